@@ -2,6 +2,7 @@
 """bench.py -- verified candidates/s on MI355X (BASELINE.json metric), one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload odt|office|pdf_r34|pdf_r6|...]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,6 +15,11 @@ the ranks all-reduce (RCCL, MIN) the lowest hit index -- the early-stop exchange
 
 Inputs are resident by construction: candidates are enumerated on the device from their index, so
 nothing is copied host->device inside the timed region except the 320-byte kernel arguments.
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds the legs that take
+runs of their own: the CPU baselines (the reference's verify() on the host), every other format's GPU leg
+(`per_format`) and the configs[4] server + GPU client leg.  `--dump-outputs DIR` writes what the last timed
+step returned to its caller as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import ctypes
@@ -227,11 +233,13 @@ def shard(step, rank, world, batch, space):
     return start, min(batch, space - start)
 
 
-def run_workload(name, ctx, rank, world, steps, warmup, sync, allreduce_min, batch=None, ndev=1, stop_on_first=False):
+def run_workload(name, ctx, rank, world, steps, warmup, sync, allreduce_min, batch=None, ndev=1, stop_on_first=False,
+                 last=None):
     """W untimed + K timed steps of `name` on this rank.  A step verifies B consecutive indices per GPU
     (ndev GPUs in this process: one multi-device library call covers ndev * B) through
     brute_force.search_round -- the exact call the product's range mode makes per round -- then the ranks
-    all-reduce (MIN) the lowest hit index, the early-stop exchange of a sharded search."""
+    all-reduce (MIN) the lowest hit index, the early-stop exchange of a sharded search.  `last`, a dict, receives
+    the last timed step: this rank's window and what the step returned (dump_outputs writes it)."""
     from dprf_amd import brute_force
     _, cs, pwlen, B, _, _ = WORKLOADS[name]
     B = (batch or B) * ndev
@@ -257,7 +265,24 @@ def run_workload(name, ctx, rank, world, steps, warmup, sync, allreduce_min, bat
         lowest = low if lowest is None else min(lowest, low)
     sync()
     dt = time.perf_counter() - t0
+    if last is not None and steps > 0:
+        start, n = shard(warmup + steps - 1, rank, world, B, space)
+        last.update(start=start, count=n, lowest=low, candidates=st["candidates"])
     return dt, stats, lowest, pwlen
+
+
+def dump_outputs(path, last):
+    """What the last timed step handed its caller, one float64 array per file (keyspace indices stay below 2^53):
+    lowest_hit_index.npy -- the step's result, the lowest hit index over all ranks, -1 when its windows hold no hit;
+    candidates.npy -- the candidates the library reports verified for this rank's window; window.npy -- that
+    window's [start, count], the step's input.  Windows depend on the arguments alone, so two builds run with the
+    same arguments can be compared file for file."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    low = last["lowest"]
+    for name, v in (("lowest_hit_index", [-1 if low >= (1 << 62) else low]), ("candidates", [last["candidates"]]),
+                    ("window", [last["start"], last["count"]])):
+        np.save(os.path.join(path, name + ".npy"), np.array(v, dtype=np.float64))
 
 
 def launch_traffic(path, workload, per_launch, build):
@@ -381,14 +406,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="odt", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=None, help="per-GPU candidates per step (default per workload)")
-    ap.add_argument("--no-side", action="store_true", help="skip the per-format side measurements")
-    ap.add_argument("--cpu-seconds", type=float, default=1.5)
-    ap.add_argument("--no-cluster", action="store_true", help="skip the configs[4] server + GPU client leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines, the per-format side legs and the configs[4] cluster leg")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the per-format side measurements")
+    ap.add_argument("--cpu-seconds", type=float, default=1.5, help="with --full: seconds per CPU baseline leg (0: none)")
+    ap.add_argument("--no-cluster", action="store_true",
+                    help="with --full: skip the configs[4] server + GPU client leg")
     ap.add_argument("--cluster-candidates", type=int, default=12 << 20)
     ap.add_argument("--side-steps", type=int, default=5, help="timed steps of each per-format leg (1 warmup)")
     ap.add_argument("--stop-on-first", action="store_true",
                     help="time the product's early-stop rounds instead of full verification of every batch")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    do_side = args.full and not args.no_side
 
     rank, world, local = dist_env()
     import torch
@@ -446,10 +479,10 @@ def main():
 
     cpu = None
     side_cpu = {}
-    if rank == 0 and n_gpus == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and n_gpus == 1 and args.cpu_seconds > 0:
         cpu = cpu_baselines(fields, cs, pwlen, seconds=args.cpu_seconds)
         log("cpu baseline:", cpu)
-        if not args.no_side:
+        if do_side:
             for name in SIDE_FORMATS:
                 if name == args.workload:
                     continue
@@ -461,9 +494,13 @@ def main():
 
     ctx = _lib.Context(fields, devices=devices)
     B = args.batch or B
+    last = {}
     dt, stats, lowest, pwlen = run_workload(args.workload, ctx, rank, world, args.steps, args.warmup, sync,
-                                            allreduce_min, B, ndev=len(devices), stop_on_first=args.stop_on_first)
+                                            allreduce_min, B, ndev=len(devices), stop_on_first=args.stop_on_first,
+                                            last=last)
     dt_max = allreduce_max(dt)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     m = summarize(stats, wkey, world, dt_max, pwlen)
     peak = work.PEAK_LANE_INSTR_PER_S
     build = _lib.build_id()
@@ -473,7 +510,7 @@ def main():
     balance = device_balance(ctx)
 
     side = {}
-    if not args.no_side:
+    if do_side:
         for name in SIDE_FORMATS:
             if name == args.workload:
                 continue
@@ -523,7 +560,7 @@ def main():
             sctx.close()
 
     cluster = None
-    if rank == 0 and n_gpus == 1 and not args.no_side and not args.no_cluster:
+    if rank == 0 and n_gpus == 1 and do_side and not args.no_cluster:
         # configs[4]: server + GPU clients over TCP on this box (2 client processes on this GPU hide each
         # other's request/parse gaps), Office test document, -pr 8 order, 2^20-candidate payloads
         sys.path.insert(0, os.path.join(HERE, "tools"))

@@ -2,6 +2,7 @@
 enumeration order, parsers."""
 import itertools
 import json
+import os
 
 import pytest
 
@@ -37,10 +38,7 @@ def test_index_order_is_itertools_product(cs, n):
 
 
 def test_odt_parser_matches_golden(streams):
-    path = "/root/reference/test/files/odt/password.odt"
-    import os
-    if not os.path.exists(path):
-        pytest.skip("reference test document not present")
+    path = os.path.join(REF_FILES, "odt", "password.odt")
     assert odt2hashes.get_hashes(path, True) == streams["odt_testdoc_e"]["stream"]
     assert odt2hashes.get_hashes(path, False) == streams["odt_testdoc_std"]["stream"]
 
@@ -64,7 +62,8 @@ def test_fastdiv_magic_exact():
             assert _fastdiv(n, d) == n // d, (n, d)
 
 
-REF_FILES = "/root/reference/test/files"
+# the reference's test documents, stored as fixtures (tests/golden/ref_docs/README.md)
+REF_FILES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_docs")
 
 
 @pytest.mark.parametrize("name,rel,kind", [("pdf_testdoc_r2", "pdf/password_1.3_v1_r2.pdf", "pdf"),
@@ -73,10 +72,7 @@ REF_FILES = "/root/reference/test/files"
 def test_parsers_reproduce_reference_streams(streams, name, rel, kind):
     """The Python-3 parsers print the reference parsers' Python-2 output (PDF streams: SURVEY.md Appendix A,
     including the escaped ')' in the R2 file's U that Python 3 truncates; Office: office2john.py's output)."""
-    import os
     path = os.path.join(REF_FILES, rel)
-    if not os.path.exists(path):
-        pytest.skip("reference test document not present")
     from dprf_amd.parsers import office2john, pdf2john
     mod = pdf2john if kind == "pdf" else office2john
     assert mod.get_hash(path) == streams[name]["stream"]
@@ -84,9 +80,6 @@ def test_parsers_reproduce_reference_streams(streams, name, rel, kind):
 
 def test_get_verification_data_uses_engine_parser_modes(streams, capsys):
     """brute_force.get_verification_data: doc type 2 uses the -e stream (brute_force.py:239)."""
-    import os
-    if not os.path.exists(REF_FILES):
-        pytest.skip("reference test documents not present")
     assert bf.get_verification_data("2", REF_FILES + "/odt/password.odt") == streams["odt_testdoc_e"]["stream"]
     assert bf.get_verification_data("3", REF_FILES + "/pdf/password_1.7_v4_r4.pdf") == streams["pdf_testdoc_r4"]["stream"]
     assert bf.get_verification_data("1", REF_FILES + "/ms/password.docx") == streams["office_testdoc"]["stream"]
