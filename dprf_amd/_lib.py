@@ -140,6 +140,16 @@ def _to_bytes(p):
     return p.encode("utf-8") if isinstance(p, str) else bytes(p)
 
 
+def _check_window(start, count):
+    """A c_uint64 parameter takes a Python int modulo 2^64 without a word: a window that does not fit 64 bits would
+    pass the library's keyspace check on its wrapped values and search some other window.  Refuse it here."""
+    start, count = int(start), int(count)
+    if start < 0 or count < 0 or start + count >= 1 << 64:
+        raise DprfError(E_INVALID, "window [%d, +%d) does not fit 64 bits: search the keyspace in windows with "
+                                   "0 <= start, 0 <= count and start + count < 2^64" % (start, count))
+    return start, count
+
+
 class Context:
     """One document on one or more GPUs: the compiled form of the verifier argv brute_force.py builds per
     candidate (brute_force.py:163-197).  ``devices``: a list of HIP ordinals (the library runs one worker
@@ -209,11 +219,12 @@ class Context:
         if isinstance(charset, str) and any(ord(ch) >= 0x80 for ch in charset):
             raise DprfError(E_CHARSET, "search_range enumerates byte symbols: charset %r has multi-byte characters "
                                        "(search_symbols enumerates characters)" % charset)
+        start, count = _check_window(start, count)
         cs = _to_bytes(charset)
         hits = (ctypes.c_uint64 * max(1, cap))()
         nh = ctypes.c_int64()
         st = Stats()
-        _check(lib().dprf_search_range(self._h, cs, len(cs), int(pwlen), int(start), int(count),
+        _check(lib().dprf_search_range(self._h, cs, len(cs), int(pwlen), start, count,
                                        1 if stop_on_first else 0, hits, cap, ctypes.byref(nh), ctypes.byref(st)))
         return list(hits[:min(nh.value, cap)]), nh.value, st.as_dict()
 
@@ -222,6 +233,7 @@ class Context:
         symbol its UTF-8 bytes; for Office the library converts each to UTF-16LE), spelled on the device (ABI 7,
         include/dprf.h dprf_search_symbols).  Returns (sorted hit indices -- keyspace indices, like search_range's --,
         total hits, stats dict).  DprfError(E_PWLEN) when a candidate could exceed a 64-byte list slot."""
+        start, count = _check_window(start, count)
         syms = [ch.encode("utf-8") for ch in charset] if isinstance(charset, str) else [bytes([b]) for b in charset]
         offs = [0]
         for b in syms:
@@ -230,9 +242,9 @@ class Context:
         hits = (ctypes.c_uint64 * max(1, cap))()
         nh = ctypes.c_int64()
         st = Stats()
-        _check(lib().dprf_search_symbols(self._h, b"".join(syms), so, len(syms), int(pwlen), int(start), int(count),
+        _check(lib().dprf_search_symbols(self._h, b"".join(syms), so, len(syms), int(pwlen), start, count,
                                          1 if stop_on_first else 0, hits, cap, ctypes.byref(nh), ctypes.byref(st)))
-        return [int(start) + h for h in hits[:min(nh.value, cap)]], nh.value, st.as_dict()
+        return [start + h for h in hits[:min(nh.value, cap)]], nh.value, st.as_dict()
 
     def verify_blob(self, blob, offsets, stop_on_first=False, cap=1 << 16):
         """verify_list without per-candidate Python work: candidate k is blob[offsets[k]:offsets[k+1]]

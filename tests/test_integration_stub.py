@@ -34,6 +34,17 @@ def test_stub_declares_every_prototype_it_calls():
         assert callable(ns[fn])
 
 
+def test_stub_refuses_keyspaces_over_64_bits_before_any_context():
+    """len(charset) ** password_range goes into a c_uint64, which ctypes fills modulo 2^64: the stub raises instead,
+    before it creates a context (so no GPU is needed to see it)."""
+    ns = _stub()
+    greek = "αβγδεζηθικλμνξοπρστυφχψω"
+    with pytest.raises(RuntimeError, match="64 bits"):
+        ns["gpu_range_symbols"](None, 14, greek)
+    with pytest.raises(RuntimeError, match="64 bits"):
+        ns["gpu_range"](None, 14)                          # 26^14 > 2^64
+
+
 def _fields(kind, pw):
     import contextlib
     import io
