@@ -10,17 +10,18 @@ import threading
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DPRF_LIB") or os.path.join(HERE, "libdprf.so")   # DPRF_LIB: A/B builds only
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 ALL_DEVICES = -1
 FMT_OFFICE, FMT_ODT, FMT_PDF = 1, 2, 3
 E_INVALID, E_DOMAIN, E_HIP, E_NODEVICE, E_PWLEN, E_CHARSET = -1, -2, -3, -4, -5, -6
 FLAG_NEVER_MATCHES, FLAG_REF_NONDETERMINISTIC = 1, 2
 MAX_PW, MAX_PW_RANGE, MAX_PW_R6 = 131071, 32, 176
+MAX_MASK_SYMBOLS = 2048
 
 EXPORTS = ["dprf_abi_version", "dprf_last_error", "dprf_device_count", "dprf_device_list", "dprf_ctx_create",
            "dprf_ctx_create_devices", "dprf_ctx_destroy", "dprf_ctx_format", "dprf_ctx_flags", "dprf_ctx_kernel",
            "dprf_ctx_devices", "dprf_search_range", "dprf_verify_list", "dprf_list_status", "dprf_build_id",
-           "dprf_plan_chunk", "dprf_ctx_last_call_devices", "dprf_search_symbols"]
+           "dprf_plan_chunk", "dprf_ctx_last_call_devices", "dprf_search_symbols", "dprf_search_mask"]
 
 
 class DprfError(RuntimeError):
@@ -91,6 +92,11 @@ def lib():
                                               ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64,
                                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Stats)]
             L.dprf_search_symbols.restype = ctypes.c_int
+            L.dprf_search_mask.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.c_uint64,
+                                           ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
+                                           ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Stats)]
+            L.dprf_search_mask.restype = ctypes.c_int
             L.dprf_verify_list.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Stats)]
@@ -244,6 +250,28 @@ class Context:
         st = Stats()
         _check(lib().dprf_search_symbols(self._h, b"".join(syms), so, len(syms), int(pwlen), start, count,
                                          1 if stop_on_first else 0, hits, cap, ctypes.byref(nh), ctypes.byref(st)))
+        return [start + h for h in hits[:min(nh.value, cap)]], nh.value, st.as_dict()
+
+    def search_mask(self, positions, start, count, stop_on_first=False, cap=1 << 16):
+        """Verify keyspace indices [start, start+count) of a mask: `positions` is one sequence of symbols per position
+        (mask.parse_mask's list of strings: each character a symbol, its UTF-8 bytes; a bytes entry gives byte
+        symbols), enumerated in itertools.product order and spelled on the device (ABI 8, include/dprf.h
+        dprf_search_mask).  Returns (sorted hit indices -- keyspace indices --, total hits, stats dict)."""
+        start, count = _check_window(start, count)
+        syms, poffs = [], [0]
+        for pos in positions:
+            syms.extend([ch.encode("utf-8") for ch in pos] if isinstance(pos, str) else [bytes([b]) for b in pos])
+            poffs.append(len(syms))
+        offs = [0]
+        for b in syms:
+            offs.append(offs[-1] + len(b))
+        so = (ctypes.c_uint32 * len(offs))(*offs)
+        po = (ctypes.c_uint32 * len(poffs))(*poffs)
+        hits = (ctypes.c_uint64 * max(1, cap))()
+        nh = ctypes.c_int64()
+        st = Stats()
+        _check(lib().dprf_search_mask(self._h, b"".join(syms), so, po, len(poffs) - 1, start, count,
+                                      1 if stop_on_first else 0, hits, cap, ctypes.byref(nh), ctypes.byref(st)))
         return [start + h for h in hits[:min(nh.value, cap)]], nh.value, st.as_dict()
 
     def verify_blob(self, blob, offsets, stop_on_first=False, cap=1 << 16):

@@ -21,6 +21,8 @@ candidates go to libdprf.so in batches, one candidate per GPU lane.  Differences
 * optional keyword arguments ``charset`` (default lowercase a-z, Python 2 ``string.lowercase`` in the C
   locale; distinct characters, any of them non-ASCII too -- :func:`check_charset`), ``devices`` (default:
   every visible gfx950 GPU) and ``checkpoint`` (a resumable cursor file for range mode, :class:`Checkpoint`).
+* mask mode (an extension; ``mask`` / ``custom_charsets``, ``--mask``): a set of characters per position
+  (:mod:`dprf_amd.mask`) instead of ``charset^N`` -- :func:`init_mask_brute_force`.
 
 The reference's four worker processes on one queue (:70-73, :92-95) are inside libdprf.so: one context
 spans the devices, and every search call fans out over them (one worker thread + HIP stream per GPU on a
@@ -34,6 +36,7 @@ import textwrap
 import time
 
 from . import _lib
+from . import mask as masks
 
 LOWERCASE = "abcdefghijklmnopqrstuvwxyz"
 ALNUM = LOWERCASE + LOWERCASE.upper() + "0123456789"   # the configs' "alnum" order: a-z A-Z 0-9
@@ -49,9 +52,13 @@ ROUND_MAX_SECONDS = 12.0         # ... but never longer (R6's 2^25-ca
 _HUGE = 1 << 62
 
 
-def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, checkpoint=None):
+def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, checkpoint=None, mask=None,
+         custom_charsets=()):
     # The common entry point (brute_force.py:39-57)
-    if not password_range and not passwords:
+    if mask is not None:
+        if password_range or passwords:
+            raise ValueError('Need to provide either a mask or a password range / password list (not both).')
+    elif not password_range and not passwords:
         raise ValueError('Need to provide a password range to generate or a list of passwords.')
     if password_range and passwords:
         raise ValueError('Need to provide either a password range or a password list (not both).')
@@ -60,6 +67,9 @@ def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, che
     print("Initializing brute-force.")
 
     try:
+        if mask is not None:
+            return init_mask_brute_force(input_data, mask, custom_charsets=custom_charsets, devices=devices,
+                                         checkpoint=checkpoint)
         if password_range and not passwords:
             return init_rangebased_brute_force(input_data, password_range, charset=charset, devices=devices,
                                                checkpoint=checkpoint)
@@ -91,16 +101,20 @@ def _report(found_pw, n, t0):
 
 
 class Checkpoint:
-    """Resumable shard cursor for range mode (an extension; the reference has none).  A JSON file records
-    which search it belongs to (SHA-256 of the verifier stream, charset, length) and the keyspace index
-    below which every candidate has been verified; it is rewritten atomically after every round, so an
-    interrupted run restarts at its last completed round."""
+    """Resumable shard cursor for range and mask mode (an extension; the reference has none).  A JSON file records
+    which search it belongs to (SHA-256 of the verifier stream and charset, length -- or, for a mask search, the mask
+    and its custom sets instead) and the keyspace index below which every candidate has been verified; it is
+    rewritten atomically after every round, so an interrupted run restarts at its last completed round.  A range
+    search's key has no mask and a mask search's no charset, so neither loads the other's file."""
 
-    def __init__(self, path, input_data, charset, pwlen):
+    def __init__(self, path, input_data, charset=None, pwlen=None, mask=None, custom=()):
         import hashlib
         self.path = path
-        self.key = {"stream_sha256": hashlib.sha256("*".join(map(str, input_data)).encode()).hexdigest(),
-                    "charset": charset, "pwlen": int(pwlen)}
+        self.key = {"stream_sha256": hashlib.sha256("*".join(map(str, input_data)).encode()).hexdigest()}
+        if mask is None:
+            self.key.update(charset=charset, pwlen=int(pwlen))
+        else:
+            self.key.update(mask=mask, custom=[c or "" for c in custom])
 
     def load(self):
         """(next index, found password or None) recorded for this search; (0, None) when there is none."""
@@ -251,23 +265,66 @@ def init_rangebased_brute_force(input_data, password_range, charset=LOWERCASE, d
                 return 1, DUMMY
         else:
             print("Checkpoint: resuming at index %d" % done)
-        space = len(charset) ** password_range
-        found, rate = None, 0.0
-        ndev = len(getattr(ctx, "devices", [0]))
-        kernel = getattr(ctx, "kernel", None)
-        first = first_round(kernel, ndev)
-        while done < space and found is None:
-            n = next_round(rate, space - done, round_seconds(kernel, rate, ndev), first)
-            idx, st = search_round(ctx, charset, password_range, done, n)
-            tried += st["candidates"]
-            rate = st["candidates"] / max(st["wall_ms"] / 1e3, 1e-9)
-            if idx is not None:
-                found = _index_to_password(idx, charset, password_range)
-            done += n
-            cp.save(done, found)
-            progress(t0, tried, space - done if found is None else 0)
-        _report(found, tried, t0)
-        return (1, found) if found is not None else (0, DEFAULT_PASSWORD)
+        return _rounds(ctx, cp, done, len(charset) ** password_range, tried, t0,
+                       lambda start, n: search_round(ctx, charset, password_range, start, n),
+                       lambda idx: _index_to_password(idx, charset, password_range))
+    finally:
+        ctx.close()
+
+
+def _rounds(ctx, cp, done, space, tried, t0, search, spell):
+    """Rounds of consecutive indices from `done` to the keyspace's end or the first round with a hit: search(start, n)
+    -> (lowest hit index or None, stats), spell(index) -> password.  Saves the cursor and reports after every round."""
+    found, rate = None, 0.0
+    ndev = len(getattr(ctx, "devices", [0]))
+    kernel = getattr(ctx, "kernel", None)
+    first = first_round(kernel, ndev)
+    while done < space and found is None:
+        n = next_round(rate, space - done, round_seconds(kernel, rate, ndev), first)
+        idx, st = search(done, n)
+        tried += st["candidates"]
+        rate = st["candidates"] / max(st["wall_ms"] / 1e3, 1e-9)
+        if idx is not None:
+            found = spell(idx)
+        done += n
+        cp.save(done, found)
+        progress(t0, tried, space - done if found is None else 0)
+    _report(found, tried, t0)
+    return (1, found) if found is not None else (0, DEFAULT_PASSWORD)
+
+
+def init_mask_brute_force(input_data, mask, custom_charsets=(), devices=None, checkpoint=None):
+    """The candidates a mask spells (dprf_amd.mask), in product order, plus "_dummy" first as in range mode: the same
+    rounds, one ctx.search_mask call each with stop_on_first, so the lowest keyspace index that verifies wins.  The
+    candidates are spelled on the device; a mask whose candidates can exceed a list slot raises DprfError(E_PWLEN)
+    (there is no host-spelled path).  checkpoint: as in range mode, keyed by the mask and its custom sets."""
+    custom_charsets = tuple(custom_charsets or ())
+    positions = masks.parse_mask(mask, custom_charsets)
+    space = masks.space(positions)
+    cp = Checkpoint(checkpoint, input_data, mask=mask, custom=custom_charsets)
+    done, prior = cp.load()
+    if prior is not None:
+        print("Checkpoint: search already finished, password '%s'" % prior)
+        return 1, prior
+    ctx = _context(input_data, devices)
+    t0 = time.time()
+    tried = 0
+    try:
+        if done == 0:
+            hits, _, _ = ctx.verify_list([DUMMY], stop_on_first=True, cap=1)
+            tried += 1
+            if hits:
+                cp.save(0, DUMMY)
+                _report(DUMMY, tried, t0)
+                return 1, DUMMY
+        else:
+            print("Checkpoint: resuming at index %d" % done)
+
+        def search(start, n):
+            hits, _, st = ctx.search_mask(positions, start, n, stop_on_first=True, cap=1)
+            return (hits[0] if hits else None), st
+
+        return _rounds(ctx, cp, done, space, tried, t0, search, lambda idx: masks.word(positions, idx))
     finally:
         ctx.close()
 
@@ -347,17 +404,36 @@ def main(argv=None):
     parser.add_argument("document_type", help="type of the protected document")
     parser.add_argument("filename", help="the protected document")
     parser.add_argument("-pr", "--passwordrange", type=int, help="password range to brute-force (i.e., 2 -> aa..zz)")
-    parser.add_argument("--charset", default=LOWERCASE, help="candidate alphabet (default a-z)")
+    parser.add_argument("--charset", default=None, help="candidate alphabet (default a-z)")
+    parser.add_argument("--mask", default=None,
+                        help="a set of characters per position instead of -pr/--charset: ?l a-z, ?u A-Z, ?d 0-9, "
+                             "?h 0-9a-f, ?H 0-9A-F, ?s specials, ?a all of ?l?u?d?s, ?1..?4 custom sets, ?? a "
+                             "question mark, anything else itself (i.e., ?u?l?l?l?d?d)")
+    for k in "1234":
+        parser.add_argument("-" + k, "--custom-charset" + k, dest="custom" + k, default=None,
+                            help="custom set ?%s of the mask (may use ?l ?u ?d ?h ?H ?s ?a)" % k)
     parser.add_argument("--devices", default=None, help="comma-separated GPU ordinals (default: all)")
     parser.add_argument("--checkpoint", default=None, help="resumable cursor file (written after every round)")
     args = parser.parse_args(argv)
+    customs = [getattr(args, "custom" + k) for k in "1234"]
+    if args.mask is not None and (args.passwordrange is not None or args.charset is not None):
+        parser.error("--mask replaces -pr/--passwordrange and --charset: give either a mask or a range")
+    if args.mask is None and any(c is not None for c in customs):
+        parser.error("-1 .. -4 define the custom sets of a --mask")
 
     stream = get_verification_data(args.document_type, args.filename)
     if not stream:
         sys.exit(0)
     devices = [int(x) for x in args.devices.split(",")] if args.devices else None
-    found, password = init(stream, args.passwordrange if args.passwordrange else 8, None,
-                           charset=args.charset, devices=devices, checkpoint=args.checkpoint)
+    if args.mask is not None:
+        while customs and customs[-1] is None:
+            customs.pop()
+        found, password = init(stream, None, None, devices=devices, checkpoint=args.checkpoint, mask=args.mask,
+                               custom_charsets=customs)
+    else:
+        found, password = init(stream, args.passwordrange if args.passwordrange else 8, None,
+                               charset=LOWERCASE if args.charset is None else args.charset, devices=devices,
+                               checkpoint=args.checkpoint)
     if not found:
         print("Password is not in brute-forced space.")
     return found, password

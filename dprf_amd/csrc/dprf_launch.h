@@ -24,6 +24,10 @@ hipError_t launch_long_prehash(const dprf_enum &e, const dprf_long_params &lp, d
  * trunc stay zero */
 hipError_t launch_spell_symbols(const dprf_enum &e, const uint32_t *symtab, uint32_t trunc, uint32_t *slots,
                                 uint8_t *lens, hipStream_t s);
+/* mask windows (dprf_search_mask): a.count candidates from the digits in a.sdig, position records and symbol pool in
+ * tab (DPRF_MASK_TAB_WORDS words, dprf_params.h), into slots[n][DPRF_SLOT_WORDS] / lens[n] as launch_spell_symbols */
+hipError_t launch_spell_mask(const dprf_mask_args &a, const uint32_t *tab, uint32_t *slots, uint8_t *lens,
+                             hipStream_t s);
 hipError_t launch_pdf_r6(const dprf_enum &e, const dprf_pdf_params &p, const dprf_aes_tables *T,
                          dprf_results *R, uint32_t cap, uint32_t stop, hipStream_t s);
 #endif

@@ -48,6 +48,25 @@ struct dprf_long_params {
     uint32_t target[8];             /* R5: U[0:32] as BE words                                              */
 };
 
+/* Mask windows (dprf_search_mask, k_spell_mask): a table and a radix per position.  The device table is uploaded once
+ * per call: DPRF_MASK_REC_WORDS words per position {radix, fastdiv magic m, shift s, base of the position's symbols in
+ * the pool}, then the pool's LE-packed symbol words, then its byte counts (one byte per entry).  Positions with
+ * identical symbol lists share one run of the pool.  Only the chunk start's digits change per launch: they travel in
+ * the kernel arguments. */
+#define DPRF_MASK_POOL 2048         /* = DPRF_MAX_MASK_SYMBOLS (include/dprf.h) */
+#define DPRF_MASK_REC_WORDS 4
+#define DPRF_MASK_POOL_AT (DPRF_MASK_REC_WORDS * DPRF_MAX_RANGE_LEN)
+#define DPRF_MASK_LENS_AT (DPRF_MASK_POOL_AT + DPRF_MASK_POOL)
+#define DPRF_MASK_TAB_WORDS (DPRF_MASK_LENS_AT + DPRF_MASK_POOL / 4)
+struct dprf_mask_args {
+    uint32_t count;                 /* candidates of the launch */
+    uint32_t npos;                  /* positions, 1..DPRF_MAX_RANGE_LEN */
+    uint32_t npool;                 /* pool entries in use, <= DPRF_MASK_POOL */
+    uint32_t trunc;                 /* bytes at or past it are never written (PDF R2-R4 32, R5 127, else ~0) */
+    uint32_t sdig[DPRF_MAX_RANGE_LEN / 4];  /* the chunk start's mixed-radix digits, one byte per position (position p
+                                               in byte p % 4 of word p / 4) */
+};
+
 /* Device results of one API call (accumulated over its launches). */
 struct dprf_results {
     uint32_t nhits;                 /* total hits (may exceed cap) */

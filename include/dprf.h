@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DPRF_ABI_VERSION 7
+#define DPRF_ABI_VERSION 8
 
 /* formats: the tag parse_verification_data extracts (brute_force.py:250) */
 #define DPRF_FMT_OFFICE 1   /* "$office$*2007*..."  ECMA-376 Standard Encryption            */
@@ -51,7 +51,9 @@ extern "C" {
 #define DPRF_E_CHARSET (-6)      /* range charset invalid: empty, NUL, a repeated byte, or a byte >= 0x80
                                     for Office (its candidates are UTF-16LE of characters); symbols
                                     (dprf_search_symbols): empty, repeated, with a NUL byte or over 4
-                                    bytes, or for Office not one valid UTF-8 character            */
+                                    bytes, or for Office not one valid UTF-8 character; a mask
+                                    (dprf_search_mask): the same per position, a position with no or
+                                    over 256 symbols, or over DPRF_MAX_MASK_SYMBOLS symbols in all  */
 
 #define DPRF_ALL_DEVICES (-1)    /* dprf_ctx_create device argument: every gfx950 device visible    */
 #define DPRF_MAX_DEVICES 64
@@ -77,6 +79,7 @@ extern "C" {
 #define DPRF_MAX_PW 131071
 #define DPRF_MAX_PW_R6 176
 #define DPRF_MAX_PW_RANGE 32   /* longest fixed length for dprf_search_range */
+#define DPRF_MAX_MASK_SYMBOLS 2048   /* dprf_search_mask: symbols of a mask's distinct per-position lists, summed */
 
 typedef struct dprf_ctx dprf_ctx;
 
@@ -187,6 +190,27 @@ int dprf_search_range(dprf_ctx *ctx, const uint8_t *charset, int cslen, int pwle
 int dprf_search_symbols(dprf_ctx *ctx, const uint8_t *sym, const uint32_t *sym_off, int nsym, int pwlen,
                         uint64_t start, uint64_t count, int stop_on_first, uint64_t *hits, int64_t cap,
                         int64_t *nhits, dprf_stats *stats);
+
+/* ---- mask mode (ABI 8): a symbol list per position ("?u?l?l?l?d?d", "Inv-?d?d?d?d") ----
+ * Verifies indices [start, start+count) of the product of npos symbol lists in itertools.product order (the last
+ * position fastest): position p takes the symbols pos_off[p] .. pos_off[p+1]) of one flat list (npos+1 offsets), and
+ * symbol k of that list is the bytes sym[sym_off[k] .. sym_off[k+1]).  A literal is a position of one symbol.  With
+ * the same list at every position the enumeration is dprf_search_symbols'.  The symbol rules are dprf_search_symbols',
+ * per position: 1-4 bytes, no NUL, distinct within the position (the same symbol may appear at several positions),
+ * for Office one valid UTF-8 character each, which goes in as its UTF-16LE.
+ * DPRF_E_CHARSET: a broken symbol rule, a position with no symbol or with more than 256, or more than
+ * DPRF_MAX_MASK_SYMBOLS symbols in all once positions with identical lists are counted once.
+ * DPRF_E_PWLEN: npos outside 1..DPRF_MAX_PW_RANGE, or the longest candidate -- the sum over the positions of the
+ * position's longest symbol, after the format's truncation (PDF R2-R4 32 bytes, R5 127) -- exceeds a 64-byte slot.
+ * DPRF_E_INVALID: start + count exceeds the keyspace, the product of the positions' symbol counts (computed without
+ * wrapping: a keyspace of 2^64 or more takes any window below 2^64).
+ * The device spells every candidate into a list slot (k_spell_mask) and the list-mode kernels verify it; the
+ * position records and the symbol pool go to each device once per call, and only the chunk start's mixed-radix digits
+ * change per launch.  hits[] are indices relative to `start`; stop_on_first, multi-device chunks and the cross-device
+ * stop are as dprf_search_range's. */
+int dprf_search_mask(dprf_ctx *ctx, const uint8_t *sym, const uint32_t *sym_off, const uint32_t *pos_off, int npos,
+                     uint64_t start, uint64_t count, int stop_on_first, uint64_t *hits, int64_t cap,
+                     int64_t *nhits, dprf_stats *stats);
 
 /* ---- list mode: client payloads (init_listbased_brute_force :82-104, client.py:105) ----
  * Candidate k is blob[offsets[k] .. offsets[k+1]) (n+1 offsets).  Hits are list indices. */
