@@ -10,18 +10,21 @@ import threading
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DPRF_LIB") or os.path.join(HERE, "libdprf.so")   # DPRF_LIB: A/B builds only
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 ALL_DEVICES = -1
 FMT_OFFICE, FMT_ODT, FMT_PDF = 1, 2, 3
 E_INVALID, E_DOMAIN, E_HIP, E_NODEVICE, E_PWLEN, E_CHARSET = -1, -2, -3, -4, -5, -6
 FLAG_NEVER_MATCHES, FLAG_REF_NONDETERMINISTIC = 1, 2
 MAX_PW, MAX_PW_RANGE, MAX_PW_R6 = 131071, 32, 176
 MAX_MASK_SYMBOLS = 2048
+PDF_USER, PDF_OWNER = 0, 1
+_PDF_PASSWORDS = {"user": PDF_USER, "owner": PDF_OWNER}
 
 EXPORTS = ["dprf_abi_version", "dprf_last_error", "dprf_device_count", "dprf_device_list", "dprf_ctx_create",
            "dprf_ctx_create_devices", "dprf_ctx_destroy", "dprf_ctx_format", "dprf_ctx_flags", "dprf_ctx_kernel",
            "dprf_ctx_devices", "dprf_search_range", "dprf_verify_list", "dprf_list_status", "dprf_build_id",
-           "dprf_plan_chunk", "dprf_ctx_last_call_devices", "dprf_search_symbols", "dprf_search_mask"]
+           "dprf_plan_chunk", "dprf_ctx_last_call_devices", "dprf_search_symbols", "dprf_search_mask",
+           "dprf_ctx_set_pdf_password", "dprf_ctx_pdf_password"]
 
 
 class DprfError(RuntimeError):
@@ -107,6 +110,10 @@ def lib():
             L.dprf_plan_chunk.restype = ctypes.c_uint64
             L.dprf_ctx_last_call_devices.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeviceStats), ctypes.c_int]
             L.dprf_ctx_last_call_devices.restype = ctypes.c_int
+            L.dprf_ctx_set_pdf_password.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            L.dprf_ctx_set_pdf_password.restype = ctypes.c_int
+            L.dprf_ctx_pdf_password.argtypes = [ctypes.c_void_p]
+            L.dprf_ctx_pdf_password.restype = ctypes.c_int
             if L.dprf_abi_version() != ABI_VERSION:
                 raise ImportError("libdprf.so ABI %d != %d" % (L.dprf_abi_version(), ABI_VERSION))
             _lib = L
@@ -160,9 +167,10 @@ class Context:
     """One document on one or more GPUs: the compiled form of the verifier argv brute_force.py builds per
     candidate (brute_force.py:163-197).  ``devices``: a list of HIP ordinals (the library runs one worker
     thread and one stream per entry and splits every call over them); ``device``: one ordinal, or
-    ALL_DEVICES for every gfx950 device."""
+    ALL_DEVICES for every gfx950 device.  ``pdf_password``: "user" (default) or "owner" -- which of a PDF's two
+    passwords the searches verify (ABI 9, include/dprf.h dprf_ctx_set_pdf_password)."""
 
-    def __init__(self, fields, device=0, devices=None):
+    def __init__(self, fields, device=0, devices=None, pdf_password="user"):
         fields = list(fields)
         arr = (ctypes.c_char_p * len(fields))(*[_to_bytes(f) for f in fields])
         h = ctypes.c_void_p()
@@ -178,6 +186,28 @@ class Context:
         n = lib().dprf_ctx_devices(h, out, 64)
         self.devices = list(out[:min(n, 64)])
         self.device = self.devices[0]
+        if pdf_password != "user":
+            try:
+                self.set_pdf_password(pdf_password)
+            except Exception:
+                self.close()
+                raise
+
+    def set_pdf_password(self, which):
+        """Select the password every later search / verify call on this context checks: "user" or "owner".  Raises
+        DprfError(E_INVALID) for a context that is not PDF, (E_DOMAIN) when /O or /U is too short for the owner
+        check; the mode is unchanged then."""
+        if which not in _PDF_PASSWORDS:
+            raise DprfError(E_INVALID, "pdf password kind %r (\"user\" or \"owner\")" % (which,))
+        _check(lib().dprf_ctx_set_pdf_password(self._h, _PDF_PASSWORDS[which]))
+
+    @property
+    def pdf_password(self):
+        """"user" or "owner" (a PDF context; DprfError(E_INVALID) otherwise)."""
+        rc = lib().dprf_ctx_pdf_password(self._h)
+        if rc < 0:
+            _check(rc)
+        return "owner" if rc == PDF_OWNER else "user"
 
     def close(self):
         if getattr(self, "_h", None):

@@ -21,6 +21,8 @@ candidates go to libdprf.so in batches, one candidate per GPU lane.  Differences
 * optional keyword arguments ``charset`` (default lowercase a-z, Python 2 ``string.lowercase`` in the C
   locale; distinct characters, any of them non-ASCII too -- :func:`check_charset`), ``devices`` (default:
   every visible gfx950 GPU) and ``checkpoint`` (a resumable cursor file for range mode, :class:`Checkpoint`).
+* owner-password search for PDF (an extension; ``owner=True``, ``--owner``): every candidate source verifies the
+  document's owner password instead of its user password (include/dprf.h dprf_ctx_set_pdf_password).
 * mask mode (an extension; ``mask`` / ``custom_charsets``, ``--mask``): a set of characters per position
   (:mod:`dprf_amd.mask`) instead of ``charset^N`` -- :func:`init_mask_brute_force`.
 
@@ -53,7 +55,7 @@ _HUGE = 1 << 62
 
 
 def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, checkpoint=None, mask=None,
-         custom_charsets=()):
+         custom_charsets=(), owner=False):
     # The common entry point (brute_force.py:39-57)
     if mask is not None:
         if password_range or passwords:
@@ -64,17 +66,19 @@ def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, che
         raise ValueError('Need to provide either a password range or a password list (not both).')
 
     input_data = parse_verification_data(stream)
+    if owner and input_data[0] != "pdf":
+        raise ValueError('Only a PDF has an owner password (--owner needs document type 3).')
     print("Initializing brute-force.")
 
     try:
         if mask is not None:
             return init_mask_brute_force(input_data, mask, custom_charsets=custom_charsets, devices=devices,
-                                         checkpoint=checkpoint)
+                                         checkpoint=checkpoint, owner=owner)
         if password_range and not passwords:
             return init_rangebased_brute_force(input_data, password_range, charset=charset, devices=devices,
-                                               checkpoint=checkpoint)
+                                               checkpoint=checkpoint, owner=owner)
         if passwords and not password_range:
-            return init_listbased_brute_force(input_data, passwords, devices=devices)
+            return init_listbased_brute_force(input_data, passwords, devices=devices, owner=owner)
     except KeyboardInterrupt:
         sys.exit(0)
 
@@ -88,16 +92,20 @@ def _devices(devices):
     return list(devices)
 
 
-def _context(input_data, devices):
-    """One library context over the devices (the library splits every call over them)."""
+def _context(input_data, devices, owner=False):
+    """One library context over the devices (the library splits every call over them).  owner: every call on it
+    verifies the PDF's owner password -- the mode lives in the context, so each candidate source (range, symbols and
+    their host-spelled fallback, mask, list) checks the same password."""
+    if owner:
+        return _lib.Context(input_data, devices=_devices(devices), pdf_password="owner")
     return _lib.Context(input_data, devices=_devices(devices))
 
 
-def _report(found_pw, n, t0):
+def _report(found_pw, n, t0, owner=False):
     dt = max(time.time() - t0, 1e-9)
     print("Tried %d candidates in %.3f s (%.0f H/sec)" % (n, dt, n / dt))
     if found_pw is not None:
-        print("Correct password is '" + found_pw + "'")
+        print("Correct password is '" + found_pw + "'" + (" (owner password)" if owner else ""))
 
 
 class Checkpoint:
@@ -105,16 +113,21 @@ class Checkpoint:
     which search it belongs to (SHA-256 of the verifier stream and charset, length -- or, for a mask search, the mask
     and its custom sets instead) and the keyspace index below which every candidate has been verified; it is
     rewritten atomically after every round, so an interrupted run restarts at its last completed round.  A range
-    search's key has no mask and a mask search's no charset, so neither loads the other's file."""
+    search's key has no mask and a mask search's no charset, so neither loads the other's file.  An owner-password
+    search's key carries "target": "owner"; a user search's key is as it always was, and a file without a target is
+    a user search's, so neither loads the other's file either."""
 
-    def __init__(self, path, input_data, charset=None, pwlen=None, mask=None, custom=()):
+    def __init__(self, path, input_data, charset=None, pwlen=None, mask=None, custom=(), target="user"):
         import hashlib
         self.path = path
+        self.target = target
         self.key = {"stream_sha256": hashlib.sha256("*".join(map(str, input_data)).encode()).hexdigest()}
         if mask is None:
             self.key.update(charset=charset, pwlen=int(pwlen))
         else:
             self.key.update(mask=mask, custom=[c or "" for c in custom])
+        if target != "user":
+            self.key.update(target=target)
 
     def load(self):
         """(next index, found password or None) recorded for this search; (0, None) when there is none."""
@@ -124,7 +137,7 @@ class Checkpoint:
             return 0, None
         with open(self.path) as f:
             d = json.load(f)
-        if any(d.get(k) != v for k, v in self.key.items()):
+        if any(d.get(k) != v for k, v in self.key.items()) or d.get("target", "user") != self.target:
             raise ValueError("checkpoint %s belongs to a different search" % self.path)
         return int(d["next_index"]), d.get("found")
 
@@ -239,7 +252,8 @@ def search_round(ctx, charset, pwlen, start, count, stop_on_first=True):
     return found, total
 
 
-def init_rangebased_brute_force(input_data, password_range, charset=LOWERCASE, devices=None, checkpoint=None):
+def init_rangebased_brute_force(input_data, password_range, charset=LOWERCASE, devices=None, checkpoint=None,
+                                owner=False):
     """charset^password_range in product order, plus "_dummy" (brute_force.py:60-79, :199-219).
 
     Rounds of consecutive indices, each one library call over all devices with stop_on_first: a round
@@ -247,12 +261,12 @@ def init_rangebased_brute_force(input_data, password_range, charset=LOWERCASE, d
     round with a hit holds the lowest hit overall.  checkpoint: path of a resumable cursor file
     (:class:`Checkpoint`).  charset: see check_charset (raises before any device work)."""
     check_charset(charset)
-    cp = Checkpoint(checkpoint, input_data, charset, password_range)
+    cp = Checkpoint(checkpoint, input_data, charset, password_range, target="owner" if owner else "user")
     done, prior = cp.load()
     if prior is not None:
         print("Checkpoint: search already finished, password '%s'" % prior)
         return 1, prior
-    ctx = _context(input_data, devices)
+    ctx = _context(input_data, devices, owner=True) if owner else _context(input_data, devices)
     t0 = time.time()
     tried = 0
     try:
@@ -261,18 +275,18 @@ def init_rangebased_brute_force(input_data, password_range, charset=LOWERCASE, d
             tried += 1
             if hits:
                 cp.save(0, DUMMY)
-                _report(DUMMY, tried, t0)
+                _report(DUMMY, tried, t0, owner)
                 return 1, DUMMY
         else:
             print("Checkpoint: resuming at index %d" % done)
         return _rounds(ctx, cp, done, len(charset) ** password_range, tried, t0,
                        lambda start, n: search_round(ctx, charset, password_range, start, n),
-                       lambda idx: _index_to_password(idx, charset, password_range))
+                       lambda idx: _index_to_password(idx, charset, password_range), owner)
     finally:
         ctx.close()
 
 
-def _rounds(ctx, cp, done, space, tried, t0, search, spell):
+def _rounds(ctx, cp, done, space, tried, t0, search, spell, owner=False):
     """Rounds of consecutive indices from `done` to the keyspace's end or the first round with a hit: search(start, n)
     -> (lowest hit index or None, stats), spell(index) -> password.  Saves the cursor and reports after every round."""
     found, rate = None, 0.0
@@ -289,11 +303,11 @@ def _rounds(ctx, cp, done, space, tried, t0, search, spell):
         done += n
         cp.save(done, found)
         progress(t0, tried, space - done if found is None else 0)
-    _report(found, tried, t0)
+    _report(found, tried, t0, owner)
     return (1, found) if found is not None else (0, DEFAULT_PASSWORD)
 
 
-def init_mask_brute_force(input_data, mask, custom_charsets=(), devices=None, checkpoint=None):
+def init_mask_brute_force(input_data, mask, custom_charsets=(), devices=None, checkpoint=None, owner=False):
     """The candidates a mask spells (dprf_amd.mask), in product order, plus "_dummy" first as in range mode: the same
     rounds, one ctx.search_mask call each with stop_on_first, so the lowest keyspace index that verifies wins.  The
     candidates are spelled on the device; a mask whose candidates can exceed a list slot raises DprfError(E_PWLEN)
@@ -301,12 +315,12 @@ def init_mask_brute_force(input_data, mask, custom_charsets=(), devices=None, ch
     custom_charsets = tuple(custom_charsets or ())
     positions = masks.parse_mask(mask, custom_charsets)
     space = masks.space(positions)
-    cp = Checkpoint(checkpoint, input_data, mask=mask, custom=custom_charsets)
+    cp = Checkpoint(checkpoint, input_data, mask=mask, custom=custom_charsets, target="owner" if owner else "user")
     done, prior = cp.load()
     if prior is not None:
         print("Checkpoint: search already finished, password '%s'" % prior)
         return 1, prior
-    ctx = _context(input_data, devices)
+    ctx = _context(input_data, devices, owner=True) if owner else _context(input_data, devices)
     t0 = time.time()
     tried = 0
     try:
@@ -315,7 +329,7 @@ def init_mask_brute_force(input_data, mask, custom_charsets=(), devices=None, ch
             tried += 1
             if hits:
                 cp.save(0, DUMMY)
-                _report(DUMMY, tried, t0)
+                _report(DUMMY, tried, t0, owner)
                 return 1, DUMMY
         else:
             print("Checkpoint: resuming at index %d" % done)
@@ -324,21 +338,21 @@ def init_mask_brute_force(input_data, mask, custom_charsets=(), devices=None, ch
             hits, _, st = ctx.search_mask(positions, start, n, stop_on_first=True, cap=1)
             return (hits[0] if hits else None), st
 
-        return _rounds(ctx, cp, done, space, tried, t0, search, lambda idx: masks.word(positions, idx))
+        return _rounds(ctx, cp, done, space, tried, t0, search, lambda idx: masks.word(positions, idx), owner)
     finally:
         ctx.close()
 
 
-def init_listbased_brute_force(input_data, passwords, devices=None):
+def init_listbased_brute_force(input_data, passwords, devices=None, owner=False):
     """An explicit candidate list, e.g. a server payload (brute_force.py:82-104): one library call over all
     devices; the lowest list index that verifies wins."""
     passwords = list(passwords)
-    ctx = _context(input_data, devices)
+    ctx = _context(input_data, devices, owner=True) if owner else _context(input_data, devices)
     t0 = time.time()
     try:
         hits, _, _ = ctx.verify_list(passwords, stop_on_first=True, cap=1)
         found = passwords[hits[0]] if hits else None
-        _report(found, len(passwords), t0)
+        _report(found, len(passwords), t0, owner)
         return (1, found) if found is not None else (0, DEFAULT_PASSWORD)
     finally:
         ctx.close()
@@ -412,6 +426,9 @@ def main(argv=None):
     for k in "1234":
         parser.add_argument("-" + k, "--custom-charset" + k, dest="custom" + k, default=None,
                             help="custom set ?%s of the mask (may use ?l ?u ?d ?h ?H ?s ?a)" % k)
+    parser.add_argument("--owner", action="store_true",
+                        help="search the PDF's owner password (the one that lifts print / copy / edit restrictions) "
+                             "instead of its user password; document type 3 only")
     parser.add_argument("--devices", default=None, help="comma-separated GPU ordinals (default: all)")
     parser.add_argument("--checkpoint", default=None, help="resumable cursor file (written after every round)")
     args = parser.parse_args(argv)
@@ -420,6 +437,8 @@ def main(argv=None):
         parser.error("--mask replaces -pr/--passwordrange and --charset: give either a mask or a range")
     if args.mask is None and any(c is not None for c in customs):
         parser.error("-1 .. -4 define the custom sets of a --mask")
+    if args.owner and args.document_type != '3':
+        parser.error("--owner searches a PDF's owner password: document type 3 only")
 
     stream = get_verification_data(args.document_type, args.filename)
     if not stream:
@@ -429,11 +448,11 @@ def main(argv=None):
         while customs and customs[-1] is None:
             customs.pop()
         found, password = init(stream, None, None, devices=devices, checkpoint=args.checkpoint, mask=args.mask,
-                               custom_charsets=customs)
+                               custom_charsets=customs, owner=args.owner)
     else:
         found, password = init(stream, args.passwordrange if args.passwordrange else 8, None,
                                charset=LOWERCASE if args.charset is None else args.charset, devices=devices,
-                               checkpoint=args.checkpoint)
+                               checkpoint=args.checkpoint, owner=args.owner)
     if not found:
         print("Password is not in brute-forced space.")
     return found, password

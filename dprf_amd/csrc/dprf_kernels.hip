@@ -1134,6 +1134,377 @@ k_pdf_r24(dprf_enum e, dprf_pdf_params p, dprf_results *R_, uint32_t cap, uint32
     }
 }
 
+/* ================================================================== PDF R2..R4, owner password */
+/* ISO 32000-1 Algorithms 3 and 7 (include/dprf.h "owner password"): the owner key MD5((pw[:32] || PAD)[:32]) [50 more
+ * MD5s over all 16 bytes] decrypts O into x, a padded user password, and x must pass the user check above as a
+ * 32-byte candidate.  Two key derivations and two RC4 stages per candidate, on k_pdf_r24's workgroup shape. */
+
+/* The 32 padded password bytes of candidate g (pdf...c:136-137), LE words */
+template <int MODE>
+DEVI void r24_padded_pw(const dprf_enum &e, const uint8_t *cs, const uint32_t *padw, const uint32_t padtail[8],
+                        uint32_t g, uint32_t pw[8]) {
+    cand c;
+    get_candidate<MODE, false>(e, cs, g, c);
+    const uint32_t len = c.len > 32u ? 32u : c.len;
+    if (MODE == 0) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) pw[j] = c.w[j] | padtail[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            uint32_t v = c.w[j] & le_keep_mask(j, len);
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const uint32_t k = 4u * j + b;
+                if (k >= len) v |= (uint32_t)((const uint8_t *)padw)[k - len] << (8 * b);
+            }
+            pw[j] = v;
+        }
+    }
+}
+/* Owner key (Algorithm 3 steps a-d): one MD5 block over the 32 padded bytes, then for R >= 3 fifty MD5s over the whole
+ * 16-byte digest, whatever the key length (the user key's rounds hash h[0:n]) */
+template <int R>
+DEVI void r24_owner_key(const uint32_t pw[8], uint32_t h[4]) {
+    {
+        uint32_t m[16];
+#pragma unroll
+        for (int j = 0; j < 8; j++) { m[j] = pw[j]; m[8 + j] = 0u; }
+        m[8] = 0x80u;
+        m[14] = 256u;
+        md5_iv(h);
+        md5_compress(h, m);
+    }
+    if (R >= 3) {
+        for (int i = 0; i < 50; i++) {
+            uint32_t m[16];
+            m[0] = h[0]; m[1] = h[1]; m[2] = h[2]; m[3] = h[3]; m[4] = 0x80u;
+#pragma unroll
+            for (int j = 5; j < 16; j++) m[j] = 0u;
+            m[14] = 128u;
+            md5_iv(h);
+            md5_compress(h, m);
+        }
+    }
+}
+/* User key of the 32 password bytes x (r24_key's chain; x comes from the RC4 wave and may hold any byte) */
+template <int R, int NK>
+DEVI void r24_user_key(const dprf_pdf_params &p, const uint32_t x[8], uint32_t h[4]) {
+    {
+        uint32_t m[16];
+#pragma unroll
+        for (int j = 0; j < 8; j++) { m[j] = x[j]; m[8 + j] = p.tail[j]; }
+        md5_iv(h);
+        md5_compress(h, m);
+        for (uint32_t b = 0; b < p.tail_blocks; b++) {
+#pragma unroll
+            for (int j = 0; j < 16; j++) m[j] = p.tail[8 + 16 * b + j];
+            md5_compress(h, m);
+        }
+    }
+    if (R >= 3) {
+        for (int i = 0; i < 50; i++) {
+            uint32_t m[16];
+            if (NK == 16) {
+                m[0] = h[0]; m[1] = h[1]; m[2] = h[2]; m[3] = h[3]; m[4] = 0x80u;
+#pragma unroll
+                for (int j = 5; j < 16; j++) m[j] = 0u;
+                m[14] = 128u;
+            } else {
+                m[0] = h[0]; m[1] = (h[1] & 0xffu) | 0x8000u;
+#pragma unroll
+                for (int j = 2; j < 16; j++) m[j] = 0u;
+                m[14] = 40u;
+            }
+            md5_iv(h);
+            md5_compress(h, m);
+        }
+    }
+}
+
+/* One workgroup = one RC4 wave + one key wave over NBAT batches of 64 candidates, as k_pdf_r24; per batch b
+ *   O(b)  key wave: owner key of the batch's candidates
+ *   D(b)  RC4 wave: x = O decrypted under it (R2: one RC4 pass; R3/R4: passes with key ^ 19 .. key ^ 0), 32 keystream
+ *         bytes per pass -- x is only known after the last pass, so this stage has no early reject
+ *   U(b)  key wave: user key of x
+ *   C(b)  RC4 wave: k_pdf_r24's check of that key against U, early reject included
+ * pipelined in two phases per batch so that both key derivations run behind an RC4 stage:
+ *   phase A_b: RC4 wave D(b+1) | key wave U(b)        phase B_b: RC4 wave C(b) | key wave O(b+2)
+ * after the prologue O(0); D(0) | O(1).  At every phase boundary the waves swap results through the S-box area, which
+ * is free then: keys in words [0, 256), x in words [256, 768), between a barrier after the stage's last S-box access
+ * and one after the writes; a third barrier keeps the RC4 wave's next KSA off the area until the key wave has read x.
+ * The RC4 wave holds one key at a time; the key wave holds x(b+1) in registers across phase B_b. */
+template <int MODE, int R, int NK>
+__global__ void __launch_bounds__(128, 5)
+k_pdf_r24_owner(dprf_enum e, dprf_pdf_params p, dprf_results *R_, uint32_t cap, uint32_t stop_on_first) {
+    constexpr uint32_t NBAT = r24_batches<R>::v;
+    static_assert(NBAT % 2 == 0, "block_prologue counts NBAT / 2 candidates per thread of the 128-thread block");
+    __shared__ __attribute__((aligned(16))) uint8_t S[RC4_WAVE_BYTES];
+    __shared__ __attribute__((aligned(16))) uint32_t aux[64 + 16 + 4];
+    uint8_t *cs = (uint8_t *)aux;
+    uint32_t *padw = aux + 64;
+    uint32_t *flag = aux + 80;
+    if (threadIdx.x < 8) { padw[threadIdx.x] = p.pad[threadIdx.x]; padw[threadIdx.x + 8] = p.pad[threadIdx.x]; }
+    if (!block_prologue<false>(e, nullptr, R_, stop_on_first, cs, nullptr, flag, NBAT / 2)) return;
+    const uint32_t base = blockIdx.x * (64u * NBAT);
+    const uint32_t left = e.count - base;
+    const uint32_t nb = left >= 64u * NBAT ? (uint32_t)NBAT : (left + 63u) / 64u;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t *keyx = (uint32_t *)S;                       /* [4][64] key words, only inside an exchange */
+    uint32_t *xx = keyx + 256;                            /* [8][64] words of x, likewise */
+#define R24O_PUT_KEY(h) do { _Pragma("unroll") for (int q = 0; q < 4; q++) keyx[64 * q + lane] = (h)[q]; } while (0)
+#define R24O_GET_KEY(h) do { _Pragma("unroll") for (int q = 0; q < 4; q++) (h)[q] = keyx[64 * q + lane]; } while (0)
+#define R24O_PUT_X(x) do { _Pragma("unroll") for (int q = 0; q < 8; q++) xx[64 * q + lane] = (x)[q]; } while (0)
+#define R24O_GET_X(x) do { _Pragma("unroll") for (int q = 0; q < 8; q++) (x)[q] = xx[64 * q + lane]; } while (0)
+    if (threadIdx.x >= 64u) {
+        /* key wave */
+        uint32_t padtail[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) padtail[j] = 0u;
+        if (MODE == 0) {
+            const uint32_t q = e.pwlen >> 2, r = (e.pwlen & 3u) * 8u;
+#pragma unroll
+            for (int t = 0; t < 8; t++) {
+                const uint32_t lo = r ? (p.pad[t] << r) : p.pad[t];
+                const uint32_t hi = r ? (p.pad[t] >> (32u - r)) : 0u;
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    if ((uint32_t)j == q + t) padtail[j] |= lo;
+                    if ((uint32_t)j == q + t + 1) padtail[j] |= hi;
+                }
+            }
+        }
+        uint32_t h[4], x[8];
+#define R24O_OWNER_KEY(b) do {                                                                          \
+            const uint32_t g0_ = base + 64u * (b) + lane;                                               \
+            uint32_t pw_[8];                                                                            \
+            r24_padded_pw<MODE>(e, cs, padw, padtail, g0_ < e.count ? g0_ : e.count - 1, pw_);          \
+            r24_owner_key<R>(pw_, h);                                                                   \
+        } while (0)
+        R24O_OWNER_KEY(0u);
+        __syncthreads(); R24O_PUT_KEY(h); __syncthreads(); __syncthreads();          /* O(0) -> RC4 wave */
+        if (nb > 1u) R24O_OWNER_KEY(1u);
+        __syncthreads(); R24O_PUT_KEY(h); __syncthreads(); R24O_GET_X(x); __syncthreads();   /* O(1) out, x(0) in */
+#pragma unroll 1
+        for (uint32_t b = 0; b < nb; b++) {
+            r24_user_key<R, NK>(p, x, h);
+            __syncthreads(); R24O_PUT_KEY(h); __syncthreads(); R24O_GET_X(x); __syncthreads();   /* U(b) out, x(b+1) in */
+            if (b + 2u < nb) R24O_OWNER_KEY(b + 2u);
+            __syncthreads(); R24O_PUT_KEY(h); __syncthreads(); __syncthreads();      /* O(b+2) out */
+        }
+#undef R24O_OWNER_KEY
+        return;
+    }
+    /* RC4 wave */
+    __builtin_amdgcn_s_setprio(R24_PRIO);
+    uint8_t *Sw = S;
+    /* the asm KSA needs the S-box area at an LDS address with zero low 16 bits, as in k_pdf_r24 */
+    const uint32_t sbase = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) uint8_t *)S);
+    if (R24_KSA_ASM && (sbase & 0xffffu) != 0u) {
+        if (lane == 0) atomicOr(&R_->pad_, 2u);
+        for (uint32_t k = 0; k < 6u + 6u * nb; k++) __syncthreads();                 /* keep the key wave's barriers */
+        return;
+    }
+    uint32_t h[4], d[8];
+    /* D: x = O decrypted under the owner key in h */
+#define R24O_DECRYPT() do {                                                                             \
+        _Pragma("unroll") for (int j = 0; j < 8; j++) d[j] = p.o[j];                                    \
+        if (R == 2) {                                                                                   \
+            r24_ksa<5>(Sw, sbase, lane, h);                                                             \
+            rc4_prga<32>(Sw, lane << 2, d);                                                             \
+        } else if (R24_KSA_ASM) {                                                                       \
+            uint32_t kb[NK];                                                                            \
+            rc4_kb_init<NK>(h, kb);                                                                     \
+            _Pragma("unroll") for (int q = 0; q < NK; q++) kb[q] ^= 19u;                                \
+            for (uint32_t x = 19u; x < 20u; x--) {                                                      \
+                if (x != 19u) {                                                                         \
+                    const uint32_t dx = x ^ (x + 1u);                                                   \
+                    _Pragma("unroll") for (int q = 0; q < NK; q++) kb[q] ^= dx;                         \
+                }                                                                                       \
+                rc4_ksa_asm_kb<NK>(sbase, sbase + (lane << 2), kb);                                     \
+                rc4_prga<32>(Sw, lane << 2, d);                                                         \
+            }                                                                                           \
+        } else {                                                                                        \
+            for (uint32_t x = 19u; x < 20u; x--) {                                                      \
+                const uint32_t xv = x * 0x01010101u;                                                    \
+                uint32_t kx[4] = {h[0] ^ xv, h[1] ^ xv, h[2] ^ xv, h[3] ^ xv};                          \
+                rc4_ksa<NK>(Sw, lane << 2, kx);                                                         \
+                rc4_prga<32>(Sw, lane << 2, d);                                                         \
+            }                                                                                           \
+        }                                                                                               \
+    } while (0)
+    __syncthreads(); __syncthreads(); R24O_GET_KEY(h); __syncthreads();              /* O(0) */
+    R24O_DECRYPT();
+    __syncthreads(); R24O_PUT_X(d); __syncthreads(); R24O_GET_KEY(h); __syncthreads();   /* x(0) out, O(1) in */
+#pragma unroll 1
+    for (uint32_t b = 0; b < nb; b++) {
+        if (b + 1u < nb) R24O_DECRYPT();
+        __syncthreads(); R24O_PUT_X(d); __syncthreads(); R24O_GET_KEY(h); __syncthreads();   /* x(b+1) out, U(b) in */
+        /* C(b): k_pdf_r24's check with the user key of x */
+        uint32_t lid;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lid));
+        const uint32_t g = base + 64u * b + lid;
+        const bool valid = g < e.count;
+        bool ok = false;
+        if (R == 2) {
+            uint32_t c[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) c[j] = p.pad[j];
+            r24_ksa<5>(Sw, sbase, lane, h);
+            uint32_t jj = 0;
+            rc4_prga_span<1, 4>(Sw, lane << 2, c, jj);
+            if (__builtin_amdgcn_ballot_w64(valid && c[0] == p.u[0])) {
+                rc4_prga_span<5, 32>(Sw, lane << 2, c, jj);
+                ok = true;
+#pragma unroll
+                for (int j = 0; j < 8; j++) ok = ok && c[j] == p.u[j];
+            }
+        } else
+        for (uint32_t full = 0; full < 2u; full++) {
+            uint32_t c[4] = {p.h2[0], p.h2[1], p.h2[2], p.h2[3]};
+            uint32_t kb[NK];
+            rc4_kb_init<NK>(h, kb);
+            for (uint32_t x = 0; x < 20u; x++) {
+                if (R24_KSA_ASM) {
+                    const uint32_t dx = x ^ (x - 1u);
+                    if (x) {
+#pragma unroll
+                        for (int q = 0; q < NK; q++) kb[q] ^= dx;
+                    }
+                    rc4_ksa_asm_kb<NK>(sbase, sbase + (lane << 2), kb);
+                } else {
+                    const uint32_t xv = x * 0x01010101u;
+                    uint32_t kx[4] = {h[0] ^ xv, h[1] ^ xv, h[2] ^ xv, h[3] ^ xv};
+                    rc4_ksa<NK>(Sw, lane << 2, kx);
+                }
+                if (full) rc4_prga<16>(Sw, lane << 2, c);
+                else rc4_prga<2>(Sw, lane << 2, c);
+            }
+            if (full) {
+                ok = c[0] == p.u[0] && c[1] == p.u[1] && c[2] == p.u[2] && c[3] == p.u[3];
+            } else {
+                const bool pre = ((c[0] ^ p.u[0]) & 0xffffu) == 0u;
+                if (!__builtin_amdgcn_ballot_w64(valid && pre)) break;
+            }
+        }
+        if (valid && ok) report_hit(e, R_, e.start + g, cap, stop_on_first);
+        __syncthreads(); __syncthreads(); R24O_GET_KEY(h); __syncthreads();          /* O(b+2) in */
+    }
+#undef R24O_DECRYPT
+#undef R24O_PUT_KEY
+#undef R24O_GET_KEY
+#undef R24O_PUT_X
+#undef R24O_GET_X
+}
+
+/* ================================================================== PDF R5, owner password */
+/* SHA-256(pw[:127] || O[32:40] || U[0:48]) == O[0:32] (ISO 32000-2 Algorithm 12 with R5's single hash): the message is
+ * the candidate plus 56 document bytes, so two blocks for candidates up to 63 bytes and three for a 64-byte one.
+ * Range mode (NW = candidate words, one instantiation per launch length): everything past the candidate words -- the
+ * 56 bytes at offset pwlen, the terminator and the bit length -- is launch-uniform, built once per thread from the
+ * kernel arguments (scalar registers) and OR-ed onto the candidate's BE words; the second block is uniform as a whole.
+ * List mode (NW = 16): the 56 bytes sit in LDS and each lane pulls message word j from words j - len / 4 - 1 and
+ * j - len / 4 of them (a funnel shift by its own len % 4), so no lane indexes a register array.
+ * Each thread takes PER candidates 256 apart, as k_pdf_r5's list path. */
+#define R5O_PER 8
+/* 3 waves per SIMD (<= 168 VGPRs): at 4 (128) the NW = 4 range instantiation spilled 12 B per lane -- the two-block
+ * message with its uniform second block keeps more schedule terms live than k_pdf_r5's single block */
+template <int MODE, int NW>
+__global__ void __launch_bounds__(256, 3)
+k_pdf_r5_owner(dprf_enum e, dprf_pdf_params p, dprf_results *R, uint32_t cap, uint32_t stop_on_first) {
+    static_assert(NW >= 1 && NW <= DPRF_SLOT_WORDS, "candidate words");
+    __shared__ uint8_t cs[256];
+    __shared__ uint32_t flag;
+    __shared__ uint32_t suf[1 + DPRF_PDF_OSUF_WORDS + 1 + 48];    /* 0 | O[32:40] || U[0:48] | 0x80 | zeros */
+    if (MODE != 0) {
+        for (uint32_t k = threadIdx.x; k < sizeof(suf) / 4; k += blockDim.x) {
+            uint32_t v = 0u;
+#pragma unroll
+            for (int j = 0; j < DPRF_PDF_OSUF_WORDS; j++) v = k == (uint32_t)(j + 1) ? p.osuf[j] : v;
+            suf[k] = k == DPRF_PDF_OSUF_WORDS + 1u ? 0x80u : v;
+        }
+    }
+    if (!block_prologue<false>(e, nullptr, R, stop_on_first, cs, nullptr, &flag, R5O_PER)) return;
+    const uint32_t base = blockIdx.x * (blockDim.x * R5O_PER);
+    uint32_t tail[32];
+    if (MODE == 0) {
+        const uint32_t len = e.pwlen, q = len >> 2, r = (len & 3u) * 8u;
+#pragma unroll
+        for (int j = 0; j < 32; j++) tail[j] = 0u;
+#pragma unroll
+        for (int s = 0; s <= DPRF_PDF_OSUF_WORDS; s++) {
+            const uint32_t w = s < DPRF_PDF_OSUF_WORDS ? p.osuf[s < DPRF_PDF_OSUF_WORDS ? s : 0] : 0x80u;
+            const uint32_t lo = r ? (w << r) : w;
+            const uint32_t hi = r ? (w >> (32u - r)) : 0u;
+#pragma unroll
+            for (int j = 0; j < 31; j++) {
+                if ((uint32_t)j == q + s) tail[j] |= lo;
+                if ((uint32_t)j == q + s + 1) tail[j] |= hi;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 31; j++) tail[j] = bswap32(tail[j]);
+        tail[31] = (len + 56u) * 8u;
+    }
+#pragma unroll 1
+    for (uint32_t k = 0; k < (uint32_t)R5O_PER; k++) {
+        const uint32_t g0 = base + k * blockDim.x + threadIdx.x;
+        if (base + k * blockDim.x >= e.count) break;                 /* uniform */
+        const bool valid = g0 < e.count;
+        const uint32_t g = valid ? g0 : e.count - 1;
+        cand c;
+        get_candidate<MODE, false>(e, cs, g, c);
+        uint32_t hh[8];
+        sha256_iv(hh);
+        if (MODE == 0) {
+            /* range_candidate leaves the bytes past pwlen zero; pwlen <= 32: always two blocks */
+            uint32_t b[16];
+#pragma unroll
+            for (int j = 0; j < 16; j++) b[j] = (j < NW ? bswap32(c.w[j]) : 0u) | tail[j];
+            sha256_compress(hh, b);
+#pragma unroll
+            for (int j = 0; j < 16; j++) b[j] = tail[16 + j];
+            sha256_compress(hh, b);
+        } else {
+            /* the host caps list candidates of an owner search at the 64-byte slot */
+            const uint32_t len = c.len > 64u ? 64u : c.len;
+            const uint32_t q = len >> 2, r = (len & 3u) * 8u;
+            const uint32_t total = len + 56u;
+            const uint32_t nblk = (total + 9u + 63u) >> 6;            /* 2, or 3 for a 64-byte candidate */
+#pragma unroll
+            for (int blk = 0; blk < 3; blk++) {
+                if (blk == 2 && !__builtin_amdgcn_ballot_w64(nblk > 2u)) break;
+                uint32_t b[16];
+#pragma unroll
+                for (int j = 0; j < 16; j++) {
+                    const int t = 16 * blk + j;
+                    /* LE message word t: candidate bytes, then suffix byte i at message byte len + i */
+                    uint32_t v = t < DPRF_SLOT_WORDS ? (c.w[t < DPRF_SLOT_WORDS ? t : 0] & le_keep_mask(t, len)) : 0u;
+                    const uint32_t si = (uint32_t)t + 1u - q;         /* suf[] index of the word at or above this one */
+                    if ((uint32_t)t >= q) {
+                        const uint32_t lo = suf[si], below = suf[si - 1u];
+                        v |= r ? ((lo << r) | (below >> (32u - r))) : lo;
+                    }
+                    b[j] = bswap32(v);
+                }
+                if ((uint32_t)blk + 1u == nblk) b[15] = total * 8u;
+                uint32_t st[8];
+#pragma unroll
+                for (int kk = 0; kk < 8; kk++) st[kk] = hh[kk];
+                sha256_compress(st, b);
+                if ((uint32_t)blk < nblk) {
+#pragma unroll
+                    for (int kk = 0; kk < 8; kk++) hh[kk] = st[kk];
+                }
+            }
+        }
+        bool ok = true;
+#pragma unroll
+        for (int kk = 0; kk < 8; kk++) ok = ok && hh[kk] == p.o[kk];
+        if (valid && ok) report_hit(e, R, e.start + g, cap, stop_on_first);
+    }
+}
+
 #endif /* DPRF_PART_PDF */
 
 /* ------------------------------------------------------------------ launchers */
@@ -1188,6 +1559,21 @@ hipError_t launch_pdf_r5(const dprf_enum &e, const dprf_pdf_params &p, dprf_resu
                          uint32_t stop, hipStream_t s) {
 #define L5(M, NW, PER) hipLaunchKernelGGL((k_pdf_r5<M, NW, PER>), GRID(e.count, 256 * PER), dim3(256), 0, s, e, p, R, cap, stop)
 #define L5W(NW) do { if (R5_PER_MAX >= 16 && e.cslen >= 16) L5(0, NW, 16); else L5(0, NW, 8); } while (0)
+#define L5O(M, NW) hipLaunchKernelGGL((k_pdf_r5_owner<M, NW>), GRID(e.count, 256 * R5O_PER), dim3(256), 0, s, e, p, R, cap, stop)
+    if (p.owner) {
+        if (e.mode == 2) return hipErrorInvalidValue;    /* the host refuses long owner candidates */
+        if (e.mode == 0) {
+            switch ((e.pwlen + 3u) >> 2) {
+            case 0: case 1: L5O(0, 1); break;
+            case 2: L5O(0, 2); break;
+            case 3: L5O(0, 3); break;
+            case 4: L5O(0, 4); break;
+            default: L5O(0, 8); break;
+            }
+        } else {
+            L5O(1, 16);
+        }
+    } else
     if (e.mode == 0) {
         switch ((e.pwlen + 3u) >> 2) {
         case 0: case 1: L5W(1); break;
@@ -1203,6 +1589,7 @@ hipError_t launch_pdf_r5(const dprf_enum &e, const dprf_pdf_params &p, dprf_resu
     } else {
         L5(1, 8, 8);
     }
+#undef L5O
 #undef L5W
 #undef L5
     return hipGetLastError();
@@ -1210,9 +1597,16 @@ hipError_t launch_pdf_r5(const dprf_enum &e, const dprf_pdf_params &p, dprf_resu
 hipError_t launch_pdf_r24(const dprf_enum &e, const dprf_pdf_params &p, dprf_results *R, uint32_t cap,
                           uint32_t stop, hipStream_t s) {
 #define L24(M, RR, NK) hipLaunchKernelGGL((k_pdf_r24<M, RR, NK>), GRID(e.count, 64 * r24_batches<RR>::v), dim3(128), 0, s, e, p, R, cap, stop)
+#define L24O(M, RR, NK) hipLaunchKernelGGL((k_pdf_r24_owner<M, RR, NK>), GRID(e.count, 64 * r24_batches<RR>::v), dim3(128), 0, s, e, p, R, cap, stop)
+    if (p.owner) {
+        if (p.R == 2) { if (e.mode == 0) L24O(0, 2, 5); else L24O(1, 2, 5); }
+        else if (p.n == 16) { if (e.mode == 0) L24O(0, 3, 16); else L24O(1, 3, 16); }
+        else { if (e.mode == 0) L24O(0, 3, 5); else L24O(1, 3, 5); }
+    } else
     if (p.R == 2) { if (e.mode == 0) L24(0, 2, 5); else L24(1, 2, 5); }
     else if (p.n == 16) { if (e.mode == 0) L24(0, 3, 16); else L24(1, 3, 16); }
     else { if (e.mode == 0) L24(0, 3, 5); else L24(1, 3, 5); }
+#undef L24O
 #undef L24
     return hipGetLastError();
 }

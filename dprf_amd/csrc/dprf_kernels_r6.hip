@@ -220,11 +220,15 @@ DEVI void sha512_compress_pairs(uint32_t hs[16], const uint32_t lo[16], const ui
  * head of the lane's pattern column.  Returns the password length. */
 /* MODE 2 (long list, round 4): the record (<= 176 bytes, pdf...c:228) is copied word by word into the period column
  * and K0 comes from k_long_prehash (keys, [8][ncand], launch-local candidate `off`). */
-template <int MODE>
+/* OWNER (owner-password search, include/dprf.h): K = SHA256(pw || O[32:40] || U[0:48]), a message of len + 56 bytes.
+ * The 56 document bytes and the terminator are stored after pw in the slot's period column (r6_store_k overwrites them
+ * afterwards) and the two or three message blocks are read back from it word by word, so the message never sits in a
+ * register array indexed by the lane's length. */
+template <int MODE, bool OWNER = false>
 DEVI uint32_t r6_begin(const dprf_enum &e, const dprf_pdf_params &p, const uint8_t *cs, const uint8_t *sdig,
                        uint64_t idx, uint32_t off, const uint32_t *slots, const uint8_t *lens, const r6_lds &S,
                        uint32_t K[16], const uint64_t *loff = nullptr, const uint32_t *llen = nullptr,
-                       const uint32_t *keys = nullptr, uint32_t ncand = 0) {
+                       const uint32_t *keys = nullptr, uint32_t ncand = 0, uint32_t osuf_lds = 0) {
     if constexpr (MODE == 2) {
         const uint32_t len = llen[idx];
         const uint32_t *rec = slots + loff[idx];
@@ -275,6 +279,50 @@ DEVI uint32_t r6_begin(const dprf_enum &e, const dprf_pdf_params &p, const uint8
         }
         len = lens[idx];
     }
+    if constexpr (OWNER) {
+#pragma unroll
+        for (int j = 0; j < DPRF_SLOT_WORDS; j++)
+            *L32(S.pat + (((uint32_t)j << 8) | S.lanebase)) = w[j] & le_keep_mask(j, len);
+        /* the document words come from their LDS copy (r6_osuf_lds): taken from the kernel arguments here, LLVM
+         * hoists the 57 uniform byte values out of the persistent loop into long-lived VGPRs, which spill (232 B
+         * per lane) */
+#pragma unroll
+        for (int q = 0; q <= DPRF_PDF_OSUF_WORDS; q++) {
+            const uint32_t v = q < DPRF_PDF_OSUF_WORDS ? *L32(osuf_lds + 4u * q) : 0x80u;
+#pragma unroll
+            for (int b = 0; b < (q < DPRF_PDF_OSUF_WORDS ? 4 : 1); b++)
+                *L8(S.pat + pat_addr(len + 4 * q + b, S.lanebase)) = (uint8_t)(v >> (8 * b));
+        }
+        const uint32_t total = len + 4u * DPRF_PDF_OSUF_WORDS;        /* message bytes; the terminator is byte `total` */
+        const uint32_t nblk = (total + 9u + 63u) >> 6;                /* 2, or 3 for a 64-byte candidate (list mode) */
+        sha256_iv(K);
+        /* the IV as opaque values: LLVM otherwise computes the first round's terms of the constant state once, ahead
+         * of the persistent loop, and holds them in VGPRs across it -- at the kernel's VGPR limit they spilled */
+#pragma unroll
+        for (int k = 0; k < 8; k++) asm volatile("" : "+v"(K[k]));
+#pragma unroll
+        for (int blk = 0; blk < (MODE == 0 ? 2 : 3); blk++) {
+            if (blk == 2 && !__builtin_amdgcn_ballot_w64(nblk > 2u)) break;
+            uint32_t b[16], st[8];
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const uint32_t t = 16u * blk + j;
+                const uint32_t tc = 4u * t <= total ? t : total >> 2;  /* never read past the message's last word */
+                b[j] = bswap32(*L32(S.pat + ((tc << 8) | S.lanebase)) & le_keep_mask((int)t, total + 1u));
+            }
+            if ((uint32_t)blk + 1u == nblk) b[15] = total * 8u;
+#pragma unroll
+            for (int k = 0; k < 8; k++) st[k] = K[k];
+            sha256_compress(st, b);
+            if ((uint32_t)blk < nblk) {
+#pragma unroll
+                for (int k = 0; k < 8; k++) K[k] = st[k];
+            }
+        }
+#pragma unroll
+        for (int j = 8; j < 16; j++) K[j] = 0u;
+        return len;
+    }
     /* K = SHA256(pw || salt8) (:240-245): LE message with the salt at byte offset len */
     uint32_t m[32];
 #pragma unroll
@@ -313,7 +361,11 @@ DEVI uint32_t r6_begin(const dprf_enum &e, const dprf_pdf_params &p, const uint8
  * after it (a 16-byte block read starting at o < Lp then never wraps). */
 /* colbytes: the column's size in bytes -- the wrap copy stops there (range mode sizes the column to the bytes its
  * block reads can reach, launch_pdf_r6) */
-DEVI void r6_store_k(const r6_lds &S, uint32_t len, uint32_t bs, const uint32_t K[16], uint32_t colbytes) {
+/* OWNER: the period is pw || K[0:bs] || U[0:48]; the 48 document bytes (words 2..13 of the LDS copy at osuf_lds)
+ * follow K, so they move when bs changes, and the wrap copy follows them */
+template <bool OWNER = false>
+DEVI void r6_store_k(const r6_lds &S, uint32_t len, uint32_t bs, const uint32_t K[16], uint32_t colbytes,
+                     uint32_t osuf_lds = 0) {
 #pragma unroll
     for (int k = 0; k < 64; k++) {
         if ((uint32_t)k < bs) {
@@ -321,7 +373,18 @@ DEVI void r6_store_k(const r6_lds &S, uint32_t len, uint32_t bs, const uint32_t 
             *L8(S.pat + pat_addr(len + k, S.lanebase)) = (uint8_t)b;
         }
     }
-    const uint32_t Lp = len + bs;
+    if constexpr (OWNER) {
+#pragma unroll
+        for (int q = 0; q < 12; q++) {
+            const uint32_t v = *L32(osuf_lds + 8u + 4u * q);
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const uint32_t at = len + bs + 4 * q + b;
+                if (at < colbytes) *L8(S.pat + pat_addr(at, S.lanebase)) = (uint8_t)(v >> (8 * b));
+            }
+        }
+    }
+    const uint32_t Lp = len + bs + (OWNER ? 48u : 0u);
     for (uint32_t k = 0; k < 16 && Lp + k < colbytes; k++)
         *L8(S.pat + pat_addr(Lp + k, S.lanebase)) = *L8(S.pat + pat_addr(k, S.lanebase));
 }
@@ -357,14 +420,18 @@ DEVI uint32_t r6_family(const r6_lds &S, uint32_t len) {
     return sum % 3u;
 }
 
+struct r6_shared;
+DEVI uint32_t r6_osuf_lds(const r6_shared *sh);
+
 /* One round of the hardened hash for a slot whose family `hsel` is known: returns E[last]; K (16 BE
  * words, zero past the digest) and bs become the next round's; K[0:bs] is stored back into the period. */
 /* UNI (range mode): every slot of a batch has the same period length (fixed pwlen, one bs per class) and
  * every batch one family, so Lp, the block offset o and the byte selector are wave-uniform scalars and a
  * block's LDS address is one v_add of the lane's column base (~15 VALU slots per AES block saved). */
-template <bool UNI>
-DEVI uint32_t r6_round(const r6_lds &S, uint32_t len, uint32_t &bs, uint32_t hsel, uint32_t K[16], uint32_t colbytes) {
-    uint32_t Lp = len + bs;
+template <bool UNI, bool OWNER = false>
+DEVI uint32_t r6_round(const r6_lds &S, uint32_t len, uint32_t &bs, uint32_t hsel, uint32_t K[16], uint32_t colbytes,
+                       const struct r6_shared *sh = nullptr) {
+    uint32_t Lp = len + bs + (OWNER ? 48u : 0u);
     if (UNI) Lp = __builtin_amdgcn_readfirstlane(Lp);
     const uint32_t colbase = S.pat + S.lanebase;                 /* pat is only 16-byte aligned */
     r6_load_k(S, len, K);
@@ -443,7 +510,7 @@ DEVI uint32_t r6_round(const r6_lds &S, uint32_t len, uint32_t &bs, uint32_t hse
 #pragma unroll
     for (int k = 0; k < 16; k++) K[k] = hs[k];
     bs = 32u + 16u * hsel;
-    r6_store_k(S, len, bs, K, colbytes);
+    r6_store_k<OWNER>(S, len, bs, K, colbytes, OWNER ? r6_osuf_lds(sh) : 0u);
     return prev[3] & 0xffu;
 }
 
@@ -528,6 +595,15 @@ DEVI r6_lds slot_lds(uint32_t patbase, uint32_t pat_words, uint32_t te_slots, ui
     return S;
 }
 
+DEVI uint32_t lds_load(const uint32_t *p);
+/* Owner search: LDS byte address of O[32:40] || U[0:48] (14 LE words), staged once per workgroup behind the last
+ * pattern group (launch_pdf_r6 reserves the 64 bytes).  Recomputed from LDS words at every use, so neither the address
+ * nor the words (or the byte values cut from them) are held in registers across the persistent loop. */
+DEVI uint32_t r6_osuf_lds(const r6_shared *sh) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t r6_dyn[];
+    const uint32_t patbase = lds_addr(r6_dyn) + 256u + (uint32_t)((sizeof(r6_shared) + 15) / 16 * 16);
+    return patbase + ((lds_load(&sh->nslots) - lds_load(&sh->te_slots)) >> 6) * lds_load(&sh->pat_words) * 256u;
+}
 DEVI uint32_t lds_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 DEVI unsigned long long lds_load64(const unsigned long long *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -549,7 +625,7 @@ DEVI uint32_t r6_take(dprf_results *R, bool need, uint32_t lane) {
 
 /* Start candidate c (from r6_take) in `slot`; false when there is none (cursor exhausted, or skipped under
  * stop_on_first). */
-template <int MODE>
+template <int MODE, bool OWNER = false>
 DEVI bool r6_start(const dprf_enum &e, const dprf_pdf_params &p, const uint8_t *cs, dprf_results *R,
                    uint32_t stop_on_first, r6_shared *sh, const r6_lds &S, uint32_t slot, uint32_t c) {
     /* the cursor hands out candidates in increasing order, so every candidate below one that is taken has
@@ -564,9 +640,10 @@ DEVI bool r6_start(const dprf_enum &e, const dprf_pdf_params &p, const uint8_t *
     sh->cand[slot] = c;
     if (c == R6_IDLE) return false;
     uint32_t K[16];
-    const uint32_t len = r6_begin<MODE>(e, p, cs, sh->sdig, lds_load64(&sh->start) + c, c, sh->slots, sh->lens, S, K,
-                                        sh->loff, sh->llen, sh->keys, lds_load(&sh->ncand));
-    r6_store_k(S, len, 32u, K, MODE == 0 ? 4u * lds_load(&sh->pat_words) : ~0u);   /* list mode: full wrap */
+    const uint32_t len = r6_begin<MODE, OWNER>(e, p, cs, sh->sdig, lds_load64(&sh->start) + c, c, sh->slots, sh->lens, S, K,
+                                        sh->loff, sh->llen, sh->keys, lds_load(&sh->ncand), OWNER ? r6_osuf_lds(sh) : 0u);
+    r6_store_k<OWNER>(S, len, 32u, K, MODE == 0 ? 4u * lds_load(&sh->pat_words) : ~0u,
+                      OWNER ? r6_osuf_lds(sh) : 0u);                                    /* list mode: full wrap */
     sh->state[slot] = len | (32u << 8);
     return true;
 }
@@ -729,12 +806,119 @@ k_pdf_r6(dprf_enum e, dprf_pdf_params p, const dprf_aes_tables *T, dprf_results 
     }
 }
 
+/* The owner-password sibling (include/dprf.h "owner password"): k_pdf_r6's body with the owner variants of the slot
+ * functions -- period pw || K[0:bs] || U[0:48], first hash over pw || O[32:40] || U[0:48], result compared with
+ * O[0:32] -- and the document words staged in LDS (r6_osuf_lds).  A kernel of its own rather than a flag of k_pdf_r6:
+ * with the body shared through a function taking the parameters by reference, the user instantiations' argument
+ * loads were hoisted and their machine code changed.  List and range mode only (the host refuses long owner
+ * candidates). */
+template <int MODE>
+__global__ void __launch_bounds__(R6_LANES, 1)
+k_pdf_r6_owner(dprf_enum e, dprf_pdf_params p, const dprf_aes_tables *T, dprf_results *R, uint32_t cap,
+               uint32_t stop_on_first, uint32_t pat_words, uint32_t nslots, uint32_t te_slots, uint64_t idle_ticks) {
+    constexpr bool OWNER = true;
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];               /* after r6_te */
+    uint8_t *cs = (uint8_t *)smem;                                              /* 256 B */
+    r6_shared *sh = (r6_shared *)((uint8_t *)smem + 256);
+    const uint32_t patbase = lds_addr(smem) + 256u + (uint32_t)((sizeof(r6_shared) + 15) / 16 * 16);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, nthr = blockDim.x;
+    /* the asm rounds use the v_perm result as the whole LDS address: r6_te must sit at LDS address 0 (it is this
+     * kernel's only static LDS object).  A build that ever breaks this fails loudly instead of computing wrong. */
+    if (lds_addr(r6_te) != 0u) {
+        if (tid == 0) atomicOr(&R->pad_, 8u);
+        return;
+    }
+    /* the tables' copies fill each row: table t = ror(Te0, 8t) */
+    constexpr uint32_t TW = R6_TE_USED / 4;                                     /* table words per row */
+    for (uint32_t k = tid; k < 256u * TW; k += nthr) {
+        const uint32_t x = k / TW, c = k % TW, t = c / R6_TE_COPIES;
+        r6_te[x * (R6_TE_ROW_BYTES / 4) + c] = ror32(T->te0[x], 8 * t);
+    }
+    for (uint32_t k = tid; k < 64; k += nthr) ((uint32_t *)cs)[k] = ((const uint32_t *)e.charset)[k];
+    for (uint32_t k = tid; k < R6_QUEUES * R6_MAP_WORDS; k += nthr) (&sh->map[0][0])[k] = 0u;
+    if (tid < R6_QUEUES) sh->count[tid] = 0u;
+    if (tid < DPRF_MAX_RANGE_LEN) sh->sdig[tid] = e.sdig[tid];
+    if (tid == 0) {
+        sh->live = 0u;
+        sh->start = e.start;
+        sh->ncand = e.count;
+        sh->pat_words = pat_words;
+        sh->slots = e.slots;
+        sh->lens = e.lens;
+        sh->loff = e.loff;
+        sh->llen = e.llen;
+        sh->keys = e.keys;
+        if (OWNER) { sh->nslots = nslots; sh->te_slots = te_slots; }
+    }
+    if (OWNER && tid < DPRF_PDF_OSUF_WORDS) {
+        uint32_t v = 0u;
+#pragma unroll
+        for (int j = 0; j < DPRF_PDF_OSUF_WORDS; j++) v = tid == (uint32_t)j ? p.osuf[j] : v;
+        *L32(patbase + ((nslots - te_slots) >> 6) * pat_words * 256u + 4u * tid) = v;
+    }
+    __syncthreads();
+
+    for (uint32_t sl = tid; sl < nslots; sl += nthr) {
+        const r6_lds S = slot_lds(patbase, pat_words, te_slots, sl, lane);
+        if (r6_start<MODE, OWNER>(e, p, cs, R, stop_on_first, sh, S, sl, r6_take(R, true, lane))) {
+            atomicAdd(&sh->live, 1u);
+            r6_push(sh, S, sl);
+        }
+    }
+    __syncthreads();
+    if (lane == 0) sh->idle_t0[wave] = 0ull;
+    for (;;) {
+        uint32_t slot;
+        const uint32_t n = r6_claim<MODE>(sh, opaque_lane(), wave, &slot);
+        if (n == 0) {
+            if (lds_load(&sh->live) == 0u) break;                  /* uniform: one LDS word */
+            /* watchdog on the constant-rate wall clock: a wave that has found nothing queued for idle_ticks
+             * (host: 10 s; a whole launch is ~3 s and the drain after the cursor runs dry tens of ms) gives up
+             * and flags the launch instead of hanging the device; the host turns the flag into an error */
+            const uint64_t now = wall_clock64() | 1ull;                 /* never 0: 0 marks "not idling" */
+            const unsigned long long t0 = lds_load64(&sh->idle_t0[wave]);
+            if (t0 == 0ull) {
+                if (lane == 0) __hip_atomic_store(&sh->idle_t0[wave], (unsigned long long)now, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_WORKGROUP);
+            } else if (now - t0 > idle_ticks) {
+                if (lane == 0) atomicOr(&R->pad_, 1u);
+                break;
+            }
+            __builtin_amdgcn_s_sleep(4);
+            continue;
+        }
+        if (lane == 0) __hip_atomic_store(&sh->idle_t0[wave], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (slot != R6_IDLE) {
+            const r6_lds S = slot_lds(patbase, pat_words, te_slots, slot, opaque_lane());
+            const uint32_t st = sh->state[slot];
+            const uint32_t len = st & 0xffu, hs = st >> 30;
+            uint32_t bs = (st >> 8) & 0xffu, i = (st >> 16) & 0x3fffu;
+            uint32_t K[16];
+            const uint32_t last = r6_round<MODE == 0, OWNER>(S, len, bs, hs, K, MODE == 0 ? 4u * lds_load(&sh->pat_words) : ~0u, sh);
+            i++;
+            bool more = true;
+            if (i >= 64u && i >= last + 32u) {                    /* loop condition of :247 */
+                bool ok = true;
+#pragma unroll
+                for (int kk = 0; kk < 8; kk++) ok = ok && K[kk] == (OWNER ? p.o[kk] : p.u[kk]);
+                if (ok) report_hit(e, R, lds_load64(&sh->start) + sh->cand[slot], cap, stop_on_first);
+                /* the finishing lanes of the batch take their next candidates together */
+                more = r6_start<MODE, OWNER>(e, p, cs, R, stop_on_first, sh, S, slot, r6_take(R, true, opaque_lane()));
+                if (!more) atomicSub(&sh->live, 1u);
+            } else {
+                sh->state[slot] = len | (bs << 8) | (i << 16);
+            }
+            if (more) r6_push(sh, S, slot);
+        }
+    }
+}
 /* Slot capacity of one workgroup: 32-slot groups in the upper halves of the Te0 rows, then 64-slot groups
  * in the dynamic LDS left next to the table and the shared block (160 KiB per workgroup). */
 /* -pr 6 (21-word columns, r6_pat_words): 16 groups of 64 slots beside the tables and the shared block */
 static_assert(R6_TE_BYTES + 256 + (sizeof(r6_shared) + 15) / 16 * 16 + 16 * 21 * 256 <= 160 * 1024, "16 groups at -pr 6");
-static void r6_capacity(uint32_t pat_words, uint32_t *nslots, uint32_t *te_slots, size_t *shm) {
-    const size_t fixed = R6_TE_BYTES + 256 + (sizeof(r6_shared) + 15) / 16 * 16;
+/* extra: bytes kept free behind the last pattern group (owner search: 64 for the document words, r6_osuf_lds) */
+static void r6_capacity(uint32_t pat_words, uint32_t *nslots, uint32_t *te_slots, size_t *shm, size_t extra) {
+    const size_t fixed = R6_TE_BYTES + 256 + (sizeof(r6_shared) + 15) / 16 * 16 + extra;
     const uint32_t te_groups = R6_TE_USED <= 128 ? 256u / pat_words : 0u;
     uint32_t te = te_groups * 32u;
     uint32_t dyn = (uint32_t)((160u * 1024u - fixed) / ((size_t)pat_words * 256u)) * 64u;
@@ -742,7 +926,7 @@ static void r6_capacity(uint32_t pat_words, uint32_t *nslots, uint32_t *te_slots
     if (te + dyn > R6_MAX_SLOTS) dyn = (R6_MAX_SLOTS - te) / 64u * 64u;
     *te_slots = te;
     *nslots = te + dyn;
-    *shm = 256 + (sizeof(r6_shared) + 15) / 16 * 16 + (size_t)(dyn / 64u) * pat_words * 256u;   /* + static r6_te */
+    *shm = 256 + (sizeof(r6_shared) + 15) / 16 * 16 + (size_t)(dyn / 64u) * pat_words * 256u + extra;   /* + static r6_te */
 }
 
 /* Words per period column.  List mode: the period (lmax + 64) + 16 wrap bytes and the fifth word of any block read
@@ -764,10 +948,26 @@ static uint32_t r6_pat_words(uint32_t mode, uint32_t lmax) {
     }
     return mx;
 }
+/* Owner search: the same with the period 48 bytes longer (U[0:48] after K).  The first message's read-back in
+ * r6_begin (len + 57 bytes) stays inside: the block reads of the shortest period (bs = 32) already reach len + 80. */
+static uint32_t r6_pat_words_owner(uint32_t mode, uint32_t lmax) {
+    if (mode != 0) return ((lmax + 48u + 63u) >> 2) + 5u;
+    uint32_t mx = ((lmax + 16u) >> 2) + 5u;
+    for (uint32_t bs = 32; bs <= 64; bs += 16) {
+        const uint32_t Lp = lmax + bs + 48u;
+        uint32_t g = 16;
+        while (Lp % g) g >>= 1;
+        for (uint32_t o = 0; o < Lp; o += g) {
+            const uint32_t w = (o >> 2) + ((o & 3u) ? 5u : 4u);
+            if (w > mx) mx = w;
+        }
+    }
+    return mx;
+}
 
 #define R6_MAX_DEVICES 64
 static std::mutex r6_attr_mu;
-static bool r6_attr_set[3][R6_MAX_DEVICES];
+static bool r6_attr_set[5][R6_MAX_DEVICES];   /* user modes 0-2, owner modes 0-1 */
 
 hipError_t launch_pdf_r6(const dprf_enum &e, const dprf_pdf_params &p, const dprf_aes_tables *T,
                          dprf_results *R, uint32_t cap, uint32_t stop, hipStream_t s) {
@@ -775,10 +975,11 @@ hipError_t launch_pdf_r6(const dprf_enum &e, const dprf_pdf_params &p, const dpr
      * and with it the slots per CU follow the actual candidates, not the 64-byte slot width */
     const uint32_t lcap = e.mode == 2 ? (uint32_t)DPRF_R6_MAX_LONG : 4u * DPRF_SLOT_WORDS;
     const uint32_t lmax = e.pwlen < lcap ? e.pwlen : lcap;
-    const uint32_t pat_words = r6_pat_words(e.mode, lmax);
+    if (p.owner && e.mode == 2) return hipErrorInvalidValue;      /* the host refuses long owner candidates */
+    const uint32_t pat_words = p.owner ? r6_pat_words_owner(e.mode, lmax) : r6_pat_words(e.mode, lmax);
     uint32_t nslots = 0, te_slots = 0;
     size_t shm = 0;
-    r6_capacity(pat_words, &nslots, &te_slots, &shm);
+    r6_capacity(pat_words, &nslots, &te_slots, &shm, p.owner ? 64u : 0u);
     if (nslots < 64) return hipErrorInvalidValue;
     /* lanes: 12 waves, or fewer when there are fewer slots */
     uint32_t lanes = (nslots / 64u) * 64u;
@@ -798,20 +999,27 @@ hipError_t launch_pdf_r6(const dprf_enum &e, const dprf_pdf_params &p, const dpr
     /* one workgroup per CU; a launch smaller than the slots it would open uses fewer workgroups */
     uint32_t grid = (e.count + nslots - 1) / nslots;
     if (grid > (uint32_t)ncu) grid = (uint32_t)ncu;
-    const void *fn = e.mode == 0 ? (const void *)k_pdf_r6<0> : e.mode == 1 ? (const void *)k_pdf_r6<1>
+    const void *fn = p.owner ? (e.mode == 0 ? (const void *)k_pdf_r6_owner<0> : (const void *)k_pdf_r6_owner<1>)
+                     : e.mode == 0 ? (const void *)k_pdf_r6<0> : e.mode == 1 ? (const void *)k_pdf_r6<1>
                                                                             : (const void *)k_pdf_r6<2>;
     {
         /* function attributes are per device: set once per (device, mode), under a lock -- the device
          * workers of a multi-device context launch concurrently */
         std::lock_guard<std::mutex> g(r6_attr_mu);
-        bool &done = r6_attr_set[e.mode < 3 ? e.mode : 2][dev];
+        bool &done = r6_attr_set[p.owner ? 3 + (e.mode ? 1 : 0) : (e.mode < 3 ? e.mode : 2)][dev];
         if (!done) {
             me = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - R6_TE_BYTES);
             if (me != hipSuccess) return me;
             done = true;
         }
     }
-    if (e.mode == 0)
+    if (p.owner && e.mode == 0)
+        hipLaunchKernelGGL(k_pdf_r6_owner<0>, dim3(grid), dim3(lanes), shm, s, e, p, T, R, cap, stop, pat_words, nslots,
+                           te_slots, idle_ticks);
+    else if (p.owner)
+        hipLaunchKernelGGL(k_pdf_r6_owner<1>, dim3(grid), dim3(lanes), shm, s, e, p, T, R, cap, stop, pat_words, nslots,
+                           te_slots, idle_ticks);
+    else if (e.mode == 0)
         hipLaunchKernelGGL(k_pdf_r6<0>, dim3(grid), dim3(lanes), shm, s, e, p, T, R, cap, stop, pat_words, nslots,
                            te_slots, idle_ticks);
     else if (e.mode == 1)

@@ -112,6 +112,7 @@ struct dprf_odt_params {
 
 /* PDF: pdf_password_verifier.c:64-291 */
 #define DPRF_PDF_TAIL_WORDS 64
+#define DPRF_PDF_OSUF_WORDS 14
 struct dprf_pdf_params {
     uint32_t R;                     /* 2..6 */
     uint32_t n;                     /* Length / 8 (R<=4) */
@@ -121,6 +122,12 @@ struct dprf_pdf_params {
     uint32_t tail_blocks;           /* MD5 blocks after the first (initial hash, :352-402) */
     uint32_t tail[DPRF_PDF_TAIL_WORDS]; /* LE words of O||LE32(P)||ID[||FFFFFFFF] + MD5 padding,
                                            starting at message byte 32 */
+    /* owner-password check (dprf_ctx_set_pdf_password; include/dprf.h "owner password"), filled once by parse_pdf */
+    uint32_t owner;                 /* 0: the launchers pick the user kernels, 1: the owner kernels */
+    uint32_t o[8];                  /* R<=4: O[0:32] LE words (the RC4 ciphertext of the padded user password);
+                                       R5/R6: O[0:32] BE words (the owner hash) */
+    uint32_t osuf[DPRF_PDF_OSUF_WORDS]; /* R5/R6: O[32:40] || U[0:48], LE words: the 56 message bytes after the
+                                           candidate in the owner hash's first message */
 };
 
 #endif

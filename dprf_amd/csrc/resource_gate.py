@@ -31,6 +31,9 @@ SCRATCH_LIMIT = {
     "k_long_prehash": 0,      # round 4: candidates longer than a list slot
     "k_spell_symbols": 0,     # round 6: symbol windows (dprf_search_symbols)
     "k_spell_mask": 0,        # mask windows (dprf_search_mask)
+    "k_pdf_r24_owner": 0,     # owner-password search (dprf_ctx_set_pdf_password)
+    "k_pdf_r5_owner": 0,
+    "k_pdf_r6_owner": 0,
 }
 
 

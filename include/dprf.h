@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DPRF_ABI_VERSION 8
+#define DPRF_ABI_VERSION 9
 
 /* formats: the tag parse_verification_data extracts (brute_force.py:250) */
 #define DPRF_FMT_OFFICE 1   /* "$office$*2007*..."  ECMA-376 Standard Encryption            */
@@ -47,7 +47,8 @@ extern "C" {
 #define DPRF_E_HIP (-3)          /* HIP runtime error (message has the hipError string)           */
 #define DPRF_E_NODEVICE (-4)     /* no usable gfx950 device / bad device ordinal                  */
 #define DPRF_E_PWLEN (-5)        /* candidate too long: over DPRF_MAX_PW bytes (list mode; no argv string can carry
-                                    it to the reference), or a range length over DPRF_MAX_PW_RANGE  */
+                                    it to the reference), or a range length over DPRF_MAX_PW_RANGE; owner mode
+                                    (ABI 9): a PDF R5/R6 list candidate over the 64-byte slot        */
 #define DPRF_E_CHARSET (-6)      /* range charset invalid: empty, NUL, a repeated byte, or a byte >= 0x80
                                     for Office (its candidates are UTF-16LE of characters); symbols
                                     (dprf_search_symbols): empty, repeated, with a NUL byte or over 4
@@ -154,6 +155,40 @@ const char *dprf_ctx_kernel(const dprf_ctx *ctx);   /* kernel family name, e.g. 
 /* Per-device records of the context's last search / verify call (ABI 4): writes up to cap entries, returns the
  * number of devices of that call (0 before the first call). */
 int dprf_ctx_last_call_devices(const dprf_ctx *ctx, dprf_device_stats *out, int cap);
+
+/* ---- owner password (ABI 9): which of a PDF's two passwords the searches verify ----
+ * A PDF carries a user password (opens the document) and an owner password (lifts the print / copy / edit
+ * restrictions; often the only one set).  A context verifies the user password (/U: pdf...c:115-191) unless the owner
+ * check is selected here; from then on dprf_search_range, dprf_search_symbols, dprf_search_mask and dprf_verify_list
+ * verify the chosen password, with hit indices, stop_on_first, multi-device chunks, the cross-device stop, stats and
+ * dprf_list_status as before.  Selecting DPRF_PDF_USER again restores the user check exactly.  The setter takes the
+ * context's call mutex (it waits for a running call).
+ *
+ * The reference has no owner verifier ("Further work", pdf...c:20; its R6 hash takes an ownerkey it always passes as
+ * NULL); the owner check is ISO 32000-1 Algorithms 3 and 7 and ISO 32000-2 Algorithms 12 and 2.B, with the byte
+ * truncation the user check of the same revision applies.  PAD is the 32-byte padding string.
+ *   R2-R4  h = MD5((pw[:32] || PAD)[:32]); for R >= 3, 50 x h = MD5(h) over ALL 16 bytes whatever Length is (the user
+ *          key's rounds hash h[0:n]); key = h[0:n], n = 5 for R2, else Length / 8.
+ *          R2: x = RC4(key, O[0:32]).  R3/R4: x = O[0:32], then for i = 19 down to 0: x = RC4(key XOR i, x).
+ *          x is a padded user password: the candidate verifies exactly when x passes the user check as a 32-byte
+ *          candidate -- the same initial MD5 over x || O || P || ID [|| FFFFFFFF], the same 50 rounds over h[0:n], the
+ *          same RC4 passes, the same compare (32 bytes of U for R2, 16 for R3/R4).  x may hold any byte, 0x00 included;
+ *          it never leaves the device.
+ *   R5     SHA-256(pw[:127] || O[32:40] || U[0:48]) == O[0:32].
+ *   R6     the hardened hash (pdf...c:226-291) with validation salt O[32:40] and udata = U[0:48]:
+ *          K = SHA-256(pw || salt || udata), every round's data = 64 x (pw || K[0:bs] || udata); result == O[0:32].
+ *          The password is hashed whole, as in user mode.
+ * Errors (neither changes the mode): DPRF_E_INVALID -- the context is not PDF, or `which` is unknown; DPRF_E_DOMAIN --
+ * O shorter than 32 bytes (R2-R4), or O or U shorter than 48 bytes (R5/R6; the user check needs 40 bytes of U only).
+ * A DPRF_FLAG_NEVER_MATCHES context stays never-matching.  In owner mode dprf_ctx_kernel returns "pdf_r24_owner",
+ * "pdf_r5_owner" or "pdf_r6_owner", families dprf_plan_chunk knows (the user family's policy, first chunk halved).
+ * Candidate lengths in owner mode: range, symbols and mask as before; list mode R2-R4 as before (first 32 bytes); list
+ * mode R5/R6 up to the 64-byte slot -- a longer candidate is DPRF_E_PWLEN (dprf_list_status reports it per candidate):
+ * long owner candidates are not supported yet (the long-list prehash appends the 8 salt bytes, not salt || U[0:48]). */
+#define DPRF_PDF_USER 0
+#define DPRF_PDF_OWNER 1
+int dprf_ctx_set_pdf_password(dprf_ctx *ctx, int which);   /* default DPRF_PDF_USER */
+int dprf_ctx_pdf_password(const dprf_ctx *ctx);
 
 /* ---- range mode: brute_force.py -pr N (init_rangebased_brute_force :60-79, _generate :199-219) ----
  * Verifies candidates [start, start+count) of charset^pwlen in itertools.product order (leftmost
