@@ -48,6 +48,7 @@ ROUND_SECONDS = 5.0              # range mode: wall time of one library call (ch
 FIRST_ROUND = 1 << 22           # least candidates of the first round, before a rate is known
 ROUND_CHUNKS = 4                 # a round lasts at least this many of the library's largest chunks (0: fixed
                                  # FIRST_ROUND / ROUND_SECONDS only)
+SPIN_FAMILIES = ("office_agile_sha1", "office_agile_sha512")   # first_round: cost per candidate set by the document
 ROUND_MAX_SECONDS = 12.0         # ... but never longer (R6's 2^25-candidate chunks, ~9 s each, would make
                                  # multi-GPU rounds ~36 s -- the checkpoint / Ctrl-C granularity; the guided split of
                                  # dprf_plan_chunk sizes the chunks of a shorter round down by itself)
@@ -156,7 +157,11 @@ def first_round(kernel, ndev):
     """Candidates of the first range-mode round: ROUND_CHUNKS first chunks per device (the library's policy before
     a rate is measured, dprf_plan_chunk), so no device idles in round 1 and its guided tail stays short.  One device
     has no guided tail: its rounds stay at FIRST_ROUND / ROUND_SECONDS, the checkpoint and Ctrl-C granularity
-    (ADVICE r3)."""
+    (ADVICE r3).  The Office Agile families' cost per candidate is set by the document's spinCount (at 100,000 the
+    SHA-512 family verifies FIRST_ROUND candidates in most of a minute): their first round is one first chunk per
+    device, and the measured rate sizes the rounds after it."""
+    if kernel in SPIN_FAMILIES:
+        return max(1, ndev) * _lib.plan_chunk(kernel, 0.0, _HUGE, _HUGE, 1)
     if not ROUND_CHUNKS or kernel is None or ndev <= 1:
         return FIRST_ROUND
     return max(FIRST_ROUND, ROUND_CHUNKS * ndev * _lib.plan_chunk(kernel, 0.0, _HUGE, _HUGE, 1))
@@ -412,6 +417,7 @@ def main(argv=None):
 
             Actually supported formats:
                 Office Document Structure - EncryptionInfo Stream (Standard Encryption) (Office 2007)
+                Office Document Structure - EncryptionInfo Stream (Agile Encryption) (Office 2010 / 2013 and later)
                 OpenDocument - v1.2 with AES-256 in CBC mode
                 Portable Document Format - PDF 1.3 - 1.7 (Standard Security Handlers v1-5 r2-6)
             """))

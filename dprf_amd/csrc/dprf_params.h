@@ -100,6 +100,16 @@ struct dprf_office_params {
     uint32_t hash_size;             /* byte of dec(evh) that must be 0 (:168) */
 };
 
+/* Office 2010 / 2013 Agile Encryption, password key encryptor (MS-OFFCRYPTO 2.3.4.11-2.3.4.13; include/dprf.h) */
+struct dprf_agile_params {
+    uint32_t salt[4];               /* BE words of the 16 salt bytes: the first hash's prefix and both CBC IVs */
+    uint32_t evi[4];                /* encryptedVerifierHashInput (16 B), BE */
+    uint32_t evh[8];                /* encryptedVerifierHashValue[0:32], BE */
+    uint32_t spin;                  /* spinCount */
+    uint32_t sha512;                /* 0: SHA-1 ("2010"), 1: SHA-512 ("2013") */
+    uint32_t key_words;             /* keyBits / 32: 4 or 8 */
+};
+
 /* ODT: odt_password_verifier.c:51-126 */
 struct dprf_odt_params {
     uint32_t checksum[8];           /* BE */

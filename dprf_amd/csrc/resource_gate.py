@@ -34,6 +34,8 @@ SCRATCH_LIMIT = {
     "k_pdf_r24_owner": 0,     # owner-password search (dprf_ctx_set_pdf_password)
     "k_pdf_r5_owner": 0,
     "k_pdf_r6_owner": 0,
+    "k_agile_kdf": 0,         # Office 2010 / 2013 Agile Encryption (dprf_kernels_agile.hip)
+    "k_agile_check": 0,
 }
 
 

@@ -2,11 +2,12 @@
 encrypted-OOXML path of /root/reference/src/ms-offcrypto-impl/office2john.py (process_new_office
 :1728-1821), which the reference engine calls for document type 1 (brute_force.py:236).
 
-Output, Standard Encryption (Office 2007, the only form the reference verifier handles):
+Output, Standard Encryption (Office 2007, the form the reference verifier handles):
     ``<basename>:$office$*2007*<verifierHashSize>*<keySize>*<saltSize>*<salt>*<encVerifier>*<encVerifierHash[0:32]>``
 Agile Encryption (Office 2010/2013) is printed in the reference's form too
     ``<basename>:$office$*<2010|2013>*<spinCount>*<keyBits>*<saltSize>*<salt>*<encHashInput>*<encHashValue[0:32]>``
-but libdprf.so rejects it (DPRF_E_DOMAIN): the reference verifier would misread those fields.
+and libdprf.so verifies it on the device (kernel families "office_agile_sha1" / "office_agile_sha512",
+include/dprf.h "Agile"): keyBits 128 or 256, saltSize 16, spinCount up to 10,000,000.
 
 The OLE compound file (MS-CFB) is read by a small reader of our own: header, DIFAT/FAT chains,
 directory, mini stream.

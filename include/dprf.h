@@ -35,7 +35,8 @@ extern "C" {
 #define DPRF_ABI_VERSION 9
 
 /* formats: the tag parse_verification_data extracts (brute_force.py:250) */
-#define DPRF_FMT_OFFICE 1   /* "$office$*2007*..."  ECMA-376 Standard Encryption            */
+#define DPRF_FMT_OFFICE 1   /* "$office$*2007*..."  ECMA-376 Standard Encryption; "$office$*2010*..." and
+                               "$office$*2013*..." Agile Encryption (below)                  */
 #define DPRF_FMT_ODT 2      /* "$odt$*1.2*..."      ODF 1.2 AES-256-CBC / PBKDF2-HMAC-SHA1     */
 #define DPRF_FMT_PDF 3      /* "$pdf$*V*R*..."      PDF standard security handler R2..R6       */
 
@@ -48,7 +49,8 @@ extern "C" {
 #define DPRF_E_NODEVICE (-4)     /* no usable gfx950 device / bad device ordinal                  */
 #define DPRF_E_PWLEN (-5)        /* candidate too long: over DPRF_MAX_PW bytes (list mode; no argv string can carry
                                     it to the reference), or a range length over DPRF_MAX_PW_RANGE; owner mode
-                                    (ABI 9): a PDF R5/R6 list candidate over the 64-byte slot        */
+                                    (ABI 9): a PDF R5/R6 list candidate over the 64-byte slot; Office Agile: a
+                                    list candidate of more than 32 UTF-16 units                       */
 #define DPRF_E_CHARSET (-6)      /* range charset invalid: empty, NUL, a repeated byte, or a byte >= 0x80
                                     for Office (its candidates are UTF-16LE of characters); symbols
                                     (dprf_search_symbols): empty, repeated, with a NUL byte or over 4
@@ -155,6 +157,30 @@ const char *dprf_ctx_kernel(const dprf_ctx *ctx);   /* kernel family name, e.g. 
 /* Per-device records of the context's last search / verify call (ABI 4): writes up to cap entries, returns the
  * number of devices of that call (0 before the first call). */
 int dprf_ctx_last_call_devices(const dprf_ctx *ctx, dprf_device_stats *out, int cap);
+
+/* ---- Office 2010 / 2013 Agile Encryption (MS-OFFCRYPTO 2.3.4.11-2.3.4.13, password key encryptor) ----
+ * An office stream whose version field is exactly "2010" or "2013" is an Agile stream (office2john.py prints it for
+ * every password-protected .docx / .xlsx / .pptx of Office 2010 and later); any other version field is read as the
+ * 2007 Standard Encryption stream, as before.  Fields: ["office", version, spinCount, keyBits, saltSize, salt,
+ * encryptedVerifierHashInput, encryptedVerifierHashValue[0:32]].  H = SHA-1 (20 bytes) for "2010", SHA-512 (64 bytes)
+ * for "2013"; kb = keyBits / 8.
+ *   h = H(salt || UTF16LE(pw));  for i in 0 .. spinCount-1: h = H(LE32(i) || h)
+ *   key1 = H(h || fe a7 d2 76 3b 4b 9e 79), key2 = H(h || d7 aa 0f 6d 30 61 34 4e), each cut to kb bytes; where H is
+ *   shorter than kb (SHA-1 with 256 bits) padded with 0x36 up to kb
+ *   vin = AES-CBC-decrypt(key1, iv = salt, encryptedVerifierHashInput)           (16 bytes)
+ *   vhv = AES-CBC-decrypt(key2, iv = salt, encryptedVerifierHashValue[0:32])     (32 bytes)
+ *   the candidate verifies when H(vin)[0:n] == vhv[0:n], n = 20 for "2010", 32 for "2013"
+ * There is no reference verifier for this format; the definition is pinned by the public example hashes of hashcat
+ * modes 9500 / 9600 (tests/golden/agile_vectors.json).  Accepted domain, anything else DPRF_E_DOMAIN with a message
+ * naming the field: spinCount decimal in 0..DPRF_AGILE_MAX_SPIN; keyBits 128 or 256 (no AES-192); saltSize 16 with 32
+ * hex digits of salt; 32 hex digits of encryptedVerifierHashInput; 64 of encryptedVerifierHashValue.  An Agile context
+ * sets no flag.  dprf_ctx_kernel returns "office_agile_sha1" or "office_agile_sha512", families dprf_plan_chunk knows:
+ * a caller detects Agile support with dprf_plan_chunk("office_agile_sha512", 0, 1, 1, 1, 0) != 0 (DPRF_ABI_VERSION is
+ * unchanged: no export or struct changed).  Range, symbol, mask and list modes work as for the 2007 stream (ASCII
+ * range charset, one valid UTF-8 character per symbol, empty or invalid UTF-8 list candidate DPRF_E_DOMAIN), except
+ * that a list candidate of more than 32 UTF-16 units (the 64-byte slot) is DPRF_E_PWLEN, reported per candidate by
+ * dprf_list_status: long Agile candidates are not supported yet. */
+#define DPRF_AGILE_MAX_SPIN 10000000
 
 /* ---- owner password (ABI 9): which of a PDF's two passwords the searches verify ----
  * A PDF carries a user password (opens the document) and an owner password (lifts the print / copy / edit
