@@ -94,34 +94,84 @@ DEVI sha1_pre_t sha1_pre(const uint32_t st[5]) {
     asm volatile("" : "+v"(P.p0), "+v"(P.p1), "+v"(P.p2), "+v"(P.p3), "+v"(P.p4));
     return P;
 }
-/* st: the fixed starting state, out = st + the compression of w (w is overwritten by the schedule) */
-DEVI void sha1_compress_pre(const uint32_t st[5], const sha1_pre_t &P, uint32_t w[16], uint32_t out[5]) {
-    const uint32_t K = 0x5A827999u;
-    const uint32_t a1 = P.p0 + w[0];
-    const uint32_t a2 = rol32(a1, 5) + P.p1 + w[1];
-    const uint32_t a3 = rol32(a2, 5) + f_ch(a1, P.ra, P.rb) + P.p2 + w[2];
-    const uint32_t r1 = rol32(a1, 30);
-    const uint32_t a4 = rol32(a3, 5) + f_ch(a2, r1, P.ra) + P.p3 + w[3];
-    const uint32_t r2 = rol32(a2, 30);
-    const uint32_t a5 = rol32(a4, 5) + f_ch(a3, r2, r1) + P.p4 + w[4];
-    uint32_t a = a5, b = a4, c = rol32(a3, 30), d = r2, e = r1;
-#pragma unroll
-    for (int t = 5; t < 80; t++) {
-        uint32_t wt;
-        if (t < 16) {
-            wt = w[t];
-        } else {
-            wt = rol32(xor3(w[(t - 3) & 15], w[(t - 8) & 15], w[(t - 14) & 15]) ^ w[t & 15], 1);
-            w[t & 15] = wt;
-        }
+/* The message schedule of a 20-byte message behind a 64-byte prefix (PBKDF2's two HMAC compressions): W[0..4] are
+ * the message, W[5] = 0x80000000, W[6..14] = 0, W[15] = 0x2A0.  The schedule is GF(2)-linear, so the powers of its
+ * recurrence hold too:
+ *   form 1, t >= 16:  W[t] = rol1(W[t-3]  ^ W[t-8]  ^ W[t-14] ^ W[t-16])        (FIPS 180-4)
+ *   form 2, t >= 32:  W[t] = rol2(W[t-6]  ^ W[t-16] ^ W[t-28] ^ W[t-32])        (its square)
+ *   form 4, t >= 64:  W[t] = rol4(W[t-12] ^ W[t-32] ^ W[t-56] ^ W[t-64])        (its fourth power)
+ * and the longer forms land on the nine zero words where the standard one does not: t = 34..46 by form 2 and
+ * t = 64..78 by form 4 have three non-zero inputs instead of four, one v_bitop3 instead of v_bitop3 + v_xor.  A word
+ * of n non-zero inputs costs ceil((n - 1) / 2) XOR instructions and the rotate: 148 for the 64 words against the
+ * standard recurrence's 176 (sha1_h20_ops, asserted below; tests/test_odt_sha1_schedule.py restates the table).
+ * SHA1_H20_FORMS = 1 / 2 / 4 keeps the forms up to that one (A/B builds; 1 is the standard schedule). */
+#ifndef SHA1_H20_FORMS
+#define SHA1_H20_FORMS 4
+#endif
+constexpr bool sha1_h20_zero(int t) { return t >= 6 && t <= 14; }
+constexpr bool sha1_h20_const(int t) { return t == 5 || t == 15; }
+constexpr int sha1_h20_form(int t) {
+    return (SHA1_H20_FORMS >= 2 && t >= 34 && t <= 46) ? 2 : (SHA1_H20_FORMS >= 4 && t >= 64 && t <= 78) ? 4 : 1;
+}
+/* the non-zero inputs of word t, variables first (the constant, at most one, goes last: an SGPR operand) */
+struct sha1_h20_in { int n, i[4]; };
+constexpr sha1_h20_in sha1_h20_inputs(int t) {
+    const int f = sha1_h20_form(t), src[4] = {t - 3 * f, t - 8 * f, t - 14 * f, t - 16 * f};
+    sha1_h20_in r = {0, {0, 0, 0, 0}};
+    for (int pass = 0; pass < 2; pass++)
+        for (int j = 0; j < 4; j++)
+            if (!sha1_h20_zero(src[j]) && sha1_h20_const(src[j]) == (pass == 1)) r.i[r.n++] = src[j];
+    return r;
+}
+constexpr int sha1_h20_ops() {
+    int ops = 0;
+    for (int t = 16; t < 80; t++) ops += sha1_h20_inputs(t).n / 2 + 1;
+    return ops;
+}
+static_assert(sha1_h20_ops() == (SHA1_H20_FORMS >= 4 ? 148 : SHA1_H20_FORMS >= 2 ? 163 : 176), "schedule op count");
+
+template <int T> DEVI uint32_t sha1_h20_word(const uint32_t (&W)[80]) {
+    constexpr sha1_h20_in in = sha1_h20_inputs(T);
+    constexpr int f = sha1_h20_form(T);
+    uint32_t x;
+    if constexpr (in.n == 1) x = W[in.i[0]];
+    else if constexpr (in.n == 2) x = W[in.i[0]] ^ W[in.i[1]];
+    else if constexpr (in.n == 3) x = __builtin_amdgcn_bitop3_b32(W[in.i[0]], W[in.i[1]], W[in.i[2]], LUT_XOR3);
+    else x = __builtin_amdgcn_bitop3_b32(W[in.i[0]], W[in.i[1]], W[in.i[2]], LUT_XOR3) ^ W[in.i[3]];
+    return rol32(x, f);
+}
+/* rounds T..79, the schedule word of each round computed in front of it; every index is static */
+template <int T>
+DEVI void sha1_h20_rounds(uint32_t (&W)[80], uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d, uint32_t &e) {
+    if constexpr (T < 80) {
+        if constexpr (T >= 16) W[T] = sha1_h20_word<T>(W);
         uint32_t f, k;
-        if (t < 20)      { f = f_ch(b, c, d);  k = K; }
-        else if (t < 40) { f = xor3(b, c, d);  k = 0x6ED9EBA1u; }
-        else if (t < 60) { f = f_maj(b, c, d); k = 0x8F1BBCDCu; }
-        else             { f = xor3(b, c, d);  k = 0xCA62C1D6u; }
-        const uint32_t tmp = rol32(a, 5) + f + e + (k + wt);
+        if constexpr (T < 20)      { f = f_ch(b, c, d);  k = 0x5A827999u; }
+        else if constexpr (T < 40) { f = xor3(b, c, d);  k = 0x6ED9EBA1u; }
+        else if constexpr (T < 60) { f = f_maj(b, c, d); k = 0x8F1BBCDCu; }
+        else                       { f = xor3(b, c, d);  k = 0xCA62C1D6u; }
+        const uint32_t tmp = rol32(a, 5) + f + e + (k + W[T]);
         e = d; d = c; c = rol32(b, 30); b = a; a = tmp;
+        sha1_h20_rounds<T + 1>(W, a, b, c, d, e);
     }
+}
+/* st: the fixed starting state, m: the 20-byte message, out = st + the compression of m's block */
+DEVI void sha1_compress_pre(const uint32_t st[5], const sha1_pre_t &P, const uint32_t m[5], uint32_t out[5]) {
+    uint32_t W[80];
+    W[0] = m[0]; W[1] = m[1]; W[2] = m[2]; W[3] = m[3]; W[4] = m[4];
+    W[5] = 0x80000000u;
+#pragma unroll
+    for (int t = 6; t < 15; t++) W[t] = 0;
+    W[15] = (64u + 20u) * 8u;
+    const uint32_t a1 = P.p0 + W[0];
+    const uint32_t a2 = rol32(a1, 5) + P.p1 + W[1];
+    const uint32_t a3 = rol32(a2, 5) + f_ch(a1, P.ra, P.rb) + P.p2 + W[2];
+    const uint32_t r1 = rol32(a1, 30);
+    const uint32_t a4 = rol32(a3, 5) + f_ch(a2, r1, P.ra) + P.p3 + W[3];
+    const uint32_t r2 = rol32(a2, 30);
+    const uint32_t a5 = rol32(a4, 5) + f_ch(a3, r2, r1) + P.p4 + W[4];
+    uint32_t a = a5, b = a4, c = rol32(a3, 30), d = r2, e = r1;
+    sha1_h20_rounds<5>(W, a, b, c, d, e);
     out[0] = st[0] + a; out[1] = st[1] + b; out[2] = st[2] + c; out[3] = st[3] + d; out[4] = st[4] + e;
 }
 DEVI void sha1_iv(uint32_t st[5]) {

@@ -464,10 +464,15 @@ k_office_check(dprf_enum e, dprf_office_params p, const dprf_aes_tables *T, dprf
 
 #ifdef DPRF_PART_ODT
 /* ================================================================== ODF 1.2 (AES-256-CBC, PBKDF2-HMAC-SHA1) */
-/* Two launches per batch, as for Office: k_odt_kdf (SHA-256 start key + PBKDF2, 8 waves/SIMD) leaves the
+/* Two launches per batch, as for Office: k_odt_kdf (SHA-256 start key + PBKDF2, ODT_KDF_WAVES per SIMD) leaves the
  * 32-byte AES-256 key of every candidate in HBM; k_odt_check decrypts and verifies. */
+/* Waves per SIMD of k_odt_kdf.  The long-reach schedule forms of sha1_compress_pre (dev_crypto.h) keep W[0..4],
+ * W[16..22] and W[32..46] live next to the last 16 words: 96 VGPRs, 5 waves (at 6: 80 VGPRs and 40 B/lane of scratch,
+ * which the resource gate refuses).  Occupancy itself does not move this kernel: the same code bounded to 4 waves
+ * measures the same, and the standard schedule measured the same at 8 / 6 / 4 (round 2); with the squared form
+ * alone (SHA1_H20_FORMS=2) 6 and 7 waves are equal too (profiles/ab_sha1_sched.txt). */
 #ifndef ODT_KDF_WAVES
-#define ODT_KDF_WAVES 6             /* waves per SIMD: 8 / 6 / 4 measured the same (round 2); 6 leaves room for sha1_pre */
+#define ODT_KDF_WAVES 5
 #endif
 template <int MODE>
 __global__ void __launch_bounds__(256, ODT_KDF_WAVES)
@@ -491,6 +496,10 @@ k_odt_kdf(dprf_enum e, dprf_odt_params p, dprf_results *R, uint32_t stop_on_firs
         be_append<0>(m, c);
         sha256_msg2(m, c.len, sk);
     }
+    /* the key column for the stores; long list: hidden from LLVM, which otherwise keeps the loads' eight addresses
+     * live through PBKDF2 for the stores (16 VGPRs the loops need) */
+    uint32_t gk = g;
+    if constexpr (MODE == 2) asm volatile("" : "+v"(gk));
     /* PBKDF2-HMAC-SHA1(sk, salt, 1024, 32) (:85): ipad/opad midstates once per candidate */
     uint32_t ist[5], ost[5];
     {
@@ -508,30 +517,27 @@ k_odt_kdf(dprf_enum e, dprf_odt_params p, dprf_results *R, uint32_t stop_on_firs
     for (int blkno = 1; blkno <= 2; blkno++) {
         uint32_t u[5], t[5];
         {
-            uint32_t w[16] = {p.salt[0], p.salt[1], p.salt[2], p.salt[3], (uint32_t)blkno, 0x80000000u,
-                              0, 0, 0, 0, 0, 0, 0, 0, 0, (64u + 20u) * 8u};
+            /* both messages are 20 bytes: salt | INT(blkno), then the inner digest (dev_crypto.h sha1_compress_pre) */
+            const uint32_t m[5] = {p.salt[0], p.salt[1], p.salt[2], p.salt[3], (uint32_t)blkno};
             uint32_t s[5];
-            sha1_compress_pre(ist, ipre, w, s);
-            uint32_t w2[16] = {s[0], s[1], s[2], s[3], s[4], 0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 0, (64u + 20u) * 8u};
-            sha1_compress_pre(ost, opre, w2, u);
+            sha1_compress_pre(ist, ipre, m, s);
+            sha1_compress_pre(ost, opre, s, u);
         }
         t[0] = u[0]; t[1] = u[1]; t[2] = u[2]; t[3] = u[3]; t[4] = u[4];
         for (int it = 1; it < 1024; it++) {
-            uint32_t w[16] = {u[0], u[1], u[2], u[3], u[4], 0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 0, (64u + 20u) * 8u};
             uint32_t s[5];
-            sha1_compress_pre(ist, ipre, w, s);
-            uint32_t w2[16] = {s[0], s[1], s[2], s[3], s[4], 0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 0, (64u + 20u) * 8u};
-            sha1_compress_pre(ost, opre, w2, u);
+            sha1_compress_pre(ist, ipre, u, s);
+            sha1_compress_pre(ost, opre, s, u);
             t[0] ^= u[0]; t[1] ^= u[1]; t[2] ^= u[2]; t[3] ^= u[3]; t[4] ^= u[4];
         }
         /* each block's key words go out as soon as they are known (block 1's five need not stay live through
          * block 2) */
         if (blkno == 1) {
 #pragma unroll
-            for (int k = 0; k < 5; k++) keys[(size_t)k * e.count + g] = t[k];
+            for (int k = 0; k < 5; k++) keys[(size_t)k * e.count + gk] = t[k];
         } else {
 #pragma unroll
-            for (int k = 0; k < 3; k++) keys[(size_t)(5 + k) * e.count + g] = t[k];
+            for (int k = 0; k < 3; k++) keys[(size_t)(5 + k) * e.count + gk] = t[k];
         }
     }
 }
