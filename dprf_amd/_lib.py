@@ -24,7 +24,8 @@ EXPORTS = ["dprf_abi_version", "dprf_last_error", "dprf_device_count", "dprf_dev
            "dprf_ctx_create_devices", "dprf_ctx_destroy", "dprf_ctx_format", "dprf_ctx_flags", "dprf_ctx_kernel",
            "dprf_ctx_devices", "dprf_search_range", "dprf_verify_list", "dprf_list_status", "dprf_build_id",
            "dprf_plan_chunk", "dprf_ctx_last_call_devices", "dprf_search_symbols", "dprf_search_mask",
-           "dprf_ctx_set_pdf_password", "dprf_ctx_pdf_password"]
+           "dprf_ctx_set_pdf_password", "dprf_ctx_pdf_password", "dprf_ctx_set_words", "dprf_ctx_words",
+           "dprf_words_status", "dprf_search_hybrid"]
 
 
 class DprfError(RuntimeError):
@@ -114,6 +115,20 @@ def lib():
             L.dprf_ctx_set_pdf_password.restype = ctypes.c_int
             L.dprf_ctx_pdf_password.argtypes = [ctypes.c_void_p]
             L.dprf_ctx_pdf_password.restype = ctypes.c_int
+            L.dprf_ctx_set_words.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64),
+                                             ctypes.c_int64]
+            L.dprf_ctx_set_words.restype = ctypes.c_int
+            L.dprf_ctx_words.argtypes = [ctypes.c_void_p]
+            L.dprf_ctx_words.restype = ctypes.c_int64
+            L.dprf_words_status.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.c_int64, ctypes.POINTER(ctypes.c_int8)]
+            L.dprf_words_status.restype = ctypes.c_int
+            L.dprf_search_hybrid.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32),
+                                             ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64,
+                                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Stats)]
+            L.dprf_search_hybrid.restype = ctypes.c_int
             if L.dprf_abi_version() != ABI_VERSION:
                 raise ImportError("libdprf.so ABI %d != %d" % (L.dprf_abi_version(), ABI_VERSION))
             _lib = L
@@ -302,6 +317,67 @@ class Context:
         st = Stats()
         _check(lib().dprf_search_mask(self._h, b"".join(syms), so, po, len(poffs) - 1, start, count,
                                       1 if stop_on_first else 0, hits, cap, ctypes.byref(nh), ctypes.byref(st)))
+        return [start + h for h in hits[:min(nh.value, cap)]], nh.value, st.as_dict()
+
+    @staticmethod
+    def _word_blob(words):
+        import numpy as np
+        bs = [_to_bytes(w) for w in words]
+        offs = np.zeros(len(bs) + 1, dtype=np.uint64)
+        if bs:
+            np.cumsum(np.fromiter((len(b) for b in bs), dtype=np.uint64, count=len(bs)), out=offs[1:])
+        return b"".join(bs), offs
+
+    def set_words(self, words):
+        """The word table of hybrid searches (include/dprf.h dprf_ctx_set_words): a sequence of bytes / str words,
+        in order, duplicates kept; converted once and uploaded to every device of the context, where it stays until it
+        is replaced or cleared (an empty sequence).  DprfError(E_DOMAIN) for an empty word, a NUL or (Office) invalid
+        UTF-8, naming the first such word; the previous table stays then."""
+        blob, offs = self._word_blob(words)
+        _check(lib().dprf_ctx_set_words(self._h, blob, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                        len(offs) - 1))
+
+    @property
+    def words(self):
+        """The number of words the context holds (0: no table)."""
+        n = lib().dprf_ctx_words(self._h)
+        if n < 0:
+            _check(int(n))
+        return int(n)
+
+    def words_status(self, words):
+        """Per-word validity for set_words without device work: a numpy int8 array, 0 = valid, else the DPRF_E_* code
+        set_words would refuse the whole table with."""
+        import numpy as np
+        blob, offs = self._word_blob(words)
+        n = len(offs) - 1
+        st = np.zeros(max(1, n), dtype=np.int8)
+        rc = lib().dprf_words_status(self._h, blob, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n,
+                                     st.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)))
+        if rc < 0:
+            _check(rc)
+        return st[:n]
+
+    def search_hybrid(self, positions, word_at, start, count, stop_on_first=False, cap=1 << 16):
+        """Verify keyspace indices [start, start+count) of words x mask: `positions` as search_mask's (hybrid.
+        parse_hybrid's list, possibly empty), the context's word spelled before position `word_at`; index i is word
+        i // M with mask index i % M, spelled on the device (include/dprf.h dprf_search_hybrid).  Returns (sorted hit
+        indices -- keyspace indices --, total hits, stats dict)."""
+        start, count = _check_window(start, count)
+        syms, poffs = [], [0]
+        for pos in positions:
+            syms.extend([ch.encode("utf-8") for ch in pos] if isinstance(pos, str) else [bytes([b]) for b in pos])
+            poffs.append(len(syms))
+        offs = [0]
+        for b in syms:
+            offs.append(offs[-1] + len(b))
+        so = (ctypes.c_uint32 * len(offs))(*offs)
+        po = (ctypes.c_uint32 * len(poffs))(*poffs)
+        hits = (ctypes.c_uint64 * max(1, cap))()
+        nh = ctypes.c_int64()
+        st = Stats()
+        _check(lib().dprf_search_hybrid(self._h, b"".join(syms), so, po, len(poffs) - 1, int(word_at), start, count,
+                                        1 if stop_on_first else 0, hits, cap, ctypes.byref(nh), ctypes.byref(st)))
         return [start + h for h in hits[:min(nh.value, cap)]], nh.value, st.as_dict()
 
     def verify_blob(self, blob, offsets, stop_on_first=False, cap=1 << 16):

@@ -25,6 +25,8 @@ candidates go to libdprf.so in batches, one candidate per GPU lane.  Differences
   document's owner password instead of its user password (include/dprf.h dprf_ctx_set_pdf_password).
 * mask mode (an extension; ``mask`` / ``custom_charsets``, ``--mask``): a set of characters per position
   (:mod:`dprf_amd.mask`) instead of ``charset^N`` -- :func:`init_mask_brute_force`.
+* hybrid mode (an extension; ``wordlist``, ``--wordlist``): every word of a wordlist with a mask around it, the mask
+  naming the word's place with ``?w`` (:mod:`dprf_amd.hybrid`) -- :func:`init_hybrid_brute_force`.
 
 The reference's four worker processes on one queue (:70-73, :92-95) are inside libdprf.so: one context
 spans the devices, and every search call fans out over them (one worker thread + HIP stream per GPU on a
@@ -38,6 +40,7 @@ import textwrap
 import time
 
 from . import _lib
+from . import hybrid
 from . import mask as masks
 
 LOWERCASE = "abcdefghijklmnopqrstuvwxyz"
@@ -56,9 +59,19 @@ _HUGE = 1 << 62
 
 
 def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, checkpoint=None, mask=None,
-         custom_charsets=(), owner=False):
+         custom_charsets=(), owner=False, wordlist=None):
     # The common entry point (brute_force.py:39-57)
-    if mask is not None:
+    if wordlist is not None:
+        # hybrid mode: refused before any device work when it is combined with another candidate source, or when the
+        # mask has no place for the word
+        if password_range or passwords:
+            raise ValueError('Need to provide either a wordlist or a password range / password list (not both).')
+        mask = "?w" if mask is None else mask
+        try:
+            hybrid.parse_hybrid(mask, custom_charsets)
+        except _lib.DprfError as ex:
+            raise ValueError("--wordlist needs a --mask with one ?w, the word's place: %s" % ex)
+    elif mask is not None:
         if password_range or passwords:
             raise ValueError('Need to provide either a mask or a password range / password list (not both).')
     elif not password_range and not passwords:
@@ -72,6 +85,9 @@ def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, che
     print("Initializing brute-force.")
 
     try:
+        if wordlist is not None:
+            return init_hybrid_brute_force(input_data, wordlist, mask, custom_charsets=custom_charsets,
+                                           devices=devices, checkpoint=checkpoint, owner=owner)
         if mask is not None:
             return init_mask_brute_force(input_data, mask, custom_charsets=custom_charsets, devices=devices,
                                          checkpoint=checkpoint, owner=owner)
@@ -116,14 +132,20 @@ class Checkpoint:
     rewritten atomically after every round, so an interrupted run restarts at its last completed round.  A range
     search's key has no mask and a mask search's no charset, so neither loads the other's file.  An owner-password
     search's key carries "target": "owner"; a user search's key is as it always was, and a file without a target is
-    a user search's, so neither loads the other's file either."""
+    a user search's, so neither loads the other's file either.  A hybrid search (wordlist: the SHA-256 of its words
+    and their number) keeps its mask under a name of its own beside them, so it loads no mask search's file, no mask
+    search loads its file, and a changed wordlist is refused."""
 
-    def __init__(self, path, input_data, charset=None, pwlen=None, mask=None, custom=(), target="user"):
+    def __init__(self, path, input_data, charset=None, pwlen=None, mask=None, custom=(), target="user",
+                 wordlist=None):
         import hashlib
         self.path = path
         self.target = target
         self.key = {"stream_sha256": hashlib.sha256("*".join(map(str, input_data)).encode()).hexdigest()}
-        if mask is None:
+        if wordlist is not None:
+            self.key.update(hybrid_mask=mask, custom=[c or "" for c in custom], wordlist_sha256=wordlist[0],
+                            words=int(wordlist[1]))
+        elif mask is None:
             self.key.update(charset=charset, pwlen=int(pwlen))
         else:
             self.key.update(mask=mask, custom=[c or "" for c in custom])
@@ -348,6 +370,103 @@ def init_mask_brute_force(input_data, mask, custom_charsets=(), devices=None, ch
         ctx.close()
 
 
+def wordlist_key(words):
+    """What a hybrid checkpoint records of its wordlist: (SHA-256 over the words, each followed by a newline, their
+    number)."""
+    import hashlib
+    h = hashlib.sha256()
+    for w in words:
+        h.update(w + b"\n")
+    return h.hexdigest(), len(words)
+
+
+def _slot_fit(kernel, fields, words, positions):
+    """Which words fit a 64-byte list slot with this mask around them, as dprf_search_hybrid counts: the converted
+    word (Office: UTF-16LE) plus each position's longest symbol, after the format's truncation (PDF R2-R4 32 bytes
+    -- every word fits --, R5 127).  Returns a list of bools."""
+    office = fields[0] == "office"
+    wide = (lambda b: len(b.decode("utf-8").encode("utf-16-le"))) if office else len
+    room = 64 - sum(max(wide(ch.encode("utf-8")) for ch in p) for p in positions)
+    if kernel.startswith("pdf_r24"):
+        return [True] * len(words)
+    return [wide(w) <= room for w in words]
+
+
+def init_hybrid_brute_force(input_data, wordlist, mask="?w", custom_charsets=(), devices=None, checkpoint=None,
+                            owner=False):
+    """Every word of a wordlist with a mask around it (dprf_amd.hybrid: "?w?d?d", "?d?d?d?d-?w"), words in file
+    order, per word the mask in product order, plus "_dummy" first as in range mode: the same rounds, one
+    ctx.search_hybrid call each with stop_on_first, so the lowest keyspace index that verifies wins.  wordlist: a file
+    path, or a sequence of bytes words.  The word table goes to the devices once; the candidates are spelled there.
+
+    Words no candidate can contain (empty, NUL, for Office invalid UTF-8: ctx.words_status) are dropped, and so are
+    words that are too long for a list slot with this mask; their number and the reason are printed.  With the bare
+    mask "?w" the too-long words are verified at the end in one list-mode call, which takes any length.  checkpoint:
+    as in mask mode, keyed by the wordlist's SHA-256 and word count, the mask and its custom sets.  The password is
+    reported as str (UTF-8, undecodable bytes as surrogate escapes)."""
+    custom_charsets = tuple(custom_charsets or ())
+    positions, word_at = hybrid.parse_hybrid(mask, custom_charsets)
+    words = hybrid.read_wordlist(wordlist) if isinstance(wordlist, str) else [hybrid._bytes(w) for w in wordlist]
+    cp = Checkpoint(checkpoint, input_data, mask=mask, custom=custom_charsets, target="owner" if owner else "user",
+                    wordlist=wordlist_key(words))
+    done, prior = cp.load()
+    if prior is not None:
+        print("Checkpoint: search already finished, password '%s'" % prior)
+        return 1, prior
+    ctx = _context(input_data, devices, owner=True) if owner else _context(input_data, devices)
+    t0 = time.time()
+    tried = 0
+    try:
+        status = ctx.words_status(words)
+        bad = [k for k in range(len(words)) if status[k] != 0]
+        if bad:
+            print("Dropped %d words no candidate can contain (empty, a NUL byte, or for Office invalid UTF-8), the "
+                  "first is word %d" % (len(bad), bad[0] + 1))
+            words = [w for k, w in enumerate(words) if status[k] == 0]
+        fit = _slot_fit(ctx.kernel, input_data, words, positions)
+        late = [w for w, ok in zip(words, fit) if not ok]
+        if late:
+            print("Dropped %d words too long for a 64-byte candidate with this mask%s" % (
+                len(late), "; they are verified as a list at the end" if not positions else ""))
+            words = [w for w, ok in zip(words, fit) if ok]
+        space = hybrid.space(len(words), positions)
+        if done == 0:
+            hits, _, _ = ctx.verify_list([DUMMY], stop_on_first=True, cap=1)
+            tried += 1
+            if hits:
+                cp.save(0, DUMMY)
+                _report(DUMMY, tried, t0, owner)
+                return 1, DUMMY
+        else:
+            print("Checkpoint: resuming at index %d" % done)
+        if words:
+            ctx.set_words(words)
+
+        def search(start, n):
+            hits, _, st = ctx.search_hybrid(positions, word_at, start, n, stop_on_first=True, cap=1)
+            return (hits[0] if hits else None), st
+
+        if positions or not late:
+            return _rounds(ctx, cp, done, space, tried, t0, search,
+                           lambda idx: hybrid.text(hybrid.candidate(words, positions, word_at, idx)), owner)
+        # the bare word: the table first, then the words over a slot's length as one list (indices space ..)
+        found, pw = _rounds(ctx, cp, min(done, space), space, tried, t0, search,
+                            lambda idx: hybrid.text(words[idx]), owner)
+        if found or done >= space + len(late):
+            return found, pw
+        ok = ctx.list_status(b"".join(late), [0] + [sum(map(len, late[:k + 1])) for k in range(len(late))])
+        kept = [w for k, w in enumerate(late) if ok[k] == 0]
+        if len(kept) < len(late):
+            print("Dropped %d long words this format does not take in list mode" % (len(late) - len(kept)))
+        hits, _, _ = ctx.verify_list(kept, stop_on_first=True, cap=1) if kept else ([], 0, None)
+        found_pw = hybrid.text(kept[hits[0]]) if hits else None
+        cp.save(space + len(late), found_pw)
+        _report(found_pw, len(kept), t0, owner)
+        return (1, found_pw) if found_pw is not None else (0, DEFAULT_PASSWORD)
+    finally:
+        ctx.close()
+
+
 def init_listbased_brute_force(input_data, passwords, devices=None, owner=False):
     """An explicit candidate list, e.g. a server payload (brute_force.py:82-104): one library call over all
     devices; the lowest list index that verifies wins."""
@@ -432,6 +551,10 @@ def main(argv=None):
     for k in "1234":
         parser.add_argument("-" + k, "--custom-charset" + k, dest="custom" + k, default=None,
                             help="custom set ?%s of the mask (may use ?l ?u ?d ?h ?H ?s ?a)" % k)
+    parser.add_argument("--wordlist", default=None,
+                        help="hybrid search: every word of this file (one per line) with the --mask around it, the "
+                             "mask naming the word's place with ?w (i.e., ?w?d?d or ?d?d?d?d-?w; default ?w, the bare "
+                             "words)")
     parser.add_argument("--owner", action="store_true",
                         help="search the PDF's owner password (the one that lifts print / copy / edit restrictions) "
                              "instead of its user password; document type 3 only")
@@ -439,7 +562,16 @@ def main(argv=None):
     parser.add_argument("--checkpoint", default=None, help="resumable cursor file (written after every round)")
     args = parser.parse_args(argv)
     customs = [getattr(args, "custom" + k) for k in "1234"]
-    if args.mask is not None and (args.passwordrange is not None or args.charset is not None):
+    if args.wordlist is not None:
+        if args.passwordrange is not None or args.charset is not None:
+            raise ValueError("--wordlist replaces -pr/--passwordrange and --charset: give either a wordlist or a range")
+        while customs and customs[-1] is None:
+            customs.pop()
+        try:
+            hybrid.parse_hybrid("?w" if args.mask is None else args.mask, customs)
+        except _lib.DprfError as ex:
+            raise ValueError("--wordlist needs a --mask with one ?w, the word's place: %s" % ex)
+    elif args.mask is not None and (args.passwordrange is not None or args.charset is not None):
         parser.error("--mask replaces -pr/--passwordrange and --charset: give either a mask or a range")
     if args.mask is None and any(c is not None for c in customs):
         parser.error("-1 .. -4 define the custom sets of a --mask")
@@ -450,7 +582,10 @@ def main(argv=None):
     if not stream:
         sys.exit(0)
     devices = [int(x) for x in args.devices.split(",")] if args.devices else None
-    if args.mask is not None:
+    if args.wordlist is not None:
+        found, password = init(stream, None, None, devices=devices, checkpoint=args.checkpoint, mask=args.mask,
+                               custom_charsets=customs, owner=args.owner, wordlist=args.wordlist)
+    elif args.mask is not None:
         while customs and customs[-1] is None:
             customs.pop()
         found, password = init(stream, None, None, devices=devices, checkpoint=args.checkpoint, mask=args.mask,

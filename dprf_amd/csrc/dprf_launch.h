@@ -32,6 +32,10 @@ hipError_t launch_spell_symbols(const dprf_enum &e, const uint32_t *symtab, uint
  * tab (DPRF_MASK_TAB_WORDS words, dprf_params.h), into slots[n][DPRF_SLOT_WORDS] / lens[n] as launch_spell_symbols */
 hipError_t launch_spell_mask(const dprf_mask_args &a, const uint32_t *tab, uint32_t *slots, uint8_t *lens,
                              hipStream_t s);
+/* hybrid windows (dprf_search_hybrid, dprf_kernels_hybrid.hip): as launch_spell_mask with a word of the table
+ * (wblob: packed bytes as u32 words, woff: a.nwords + 1 byte offsets) spelled before mask position a.word_at */
+hipError_t launch_spell_hybrid(const dprf_hybrid_args &a, const uint32_t *tab, const uint32_t *wblob,
+                               const uint32_t *woff, uint32_t *slots, uint8_t *lens, hipStream_t s);
 hipError_t launch_pdf_r6(const dprf_enum &e, const dprf_pdf_params &p, const dprf_aes_tables *T,
                          dprf_results *R, uint32_t cap, uint32_t stop, hipStream_t s);
 #endif

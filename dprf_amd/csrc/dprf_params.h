@@ -67,6 +67,22 @@ struct dprf_mask_args {
                                                in byte p % 4 of word p / 4) */
 };
 
+/* Hybrid windows (dprf_search_hybrid, k_spell_hybrid): a word of the context's table spelled before mask position
+ * word_at, the word being one more digit at the most significant end of the mask's mixed radix.  The word table lives
+ * on the device from dprf_ctx_set_words on: the converted bytes of all words packed back to back (each clipped to a
+ * slot's 64 bytes), and nwords + 1 u32 byte offsets.  A block's 256 candidates use one contiguous run of at most
+ * DPRF_HYB_RUN words, which the block stages into LDS: at most 16 KB of bytes, read as whole u32 words from the word
+ * that holds the run's first byte (up to 3 bytes of lead-in, hence one word more). */
+#define DPRF_HYB_RUN 256
+#define DPRF_HYB_RUN_WORDS (DPRF_HYB_RUN * DPRF_SLOT_WORDS + 1)
+struct dprf_hybrid_args {
+    dprf_mask_args m;               /* the mask part; npos may be 0 here (the bare word) */
+    uint32_t word_at;               /* the word is spelled before mask position word_at, 0..npos */
+    uint32_t w0;                    /* the chunk start's word index */
+    uint32_t nwords;                /* words in the table (>= 1) */
+    uint32_t bwords;                /* u32 words the device blob holds (the staging loads stay below it) */
+};
+
 /* Device results of one API call (accumulated over its launches). */
 struct dprf_results {
     uint32_t nhits;                 /* total hits (may exceed cap) */

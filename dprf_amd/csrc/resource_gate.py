@@ -36,6 +36,7 @@ SCRATCH_LIMIT = {
     "k_pdf_r6_owner": 0,
     "k_agile_kdf": 0,         # Office 2010 / 2013 Agile Encryption (dprf_kernels_agile.hip)
     "k_agile_check": 0,
+    "k_spell_hybrid": 0,      # hybrid windows (dprf_search_hybrid, dprf_kernels_hybrid.hip)
 }
 
 

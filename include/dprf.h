@@ -285,6 +285,45 @@ int dprf_verify_list(dprf_ctx *ctx, const uint8_t *blob, const uint64_t *offsets
  * such a candidate alone, in its own verifier process (brute_force.py:163-197).  (ABI 3) */
 int dprf_list_status(const dprf_ctx *ctx, const uint8_t *blob, const uint64_t *offsets, int64_t n, int8_t *status);
 
+/* ---- hybrid mode: a word table times a mask ("Summer" x "?w?d?d?d?d!", "?d?d?d?d-?w") ----
+ * Additive to ABI 9 (no struct or earlier export changes, DPRF_ABI_VERSION stays 9): a caller detects it by looking
+ * the symbol dprf_search_hybrid up.
+ *
+ * The table: word k is blob[offsets[k] .. offsets[k+1]) (n+1 offsets), in the caller's order; a word may repeat (a
+ * wordlist's duplicates are verified twice).  dprf_ctx_set_words validates and converts all words once -- Office:
+ * UTF-8 to UTF-16LE, any number of characters; the other formats: the bytes as given -- and uploads the table to
+ * every device of the context, where it stays until it is replaced, cleared (n = 0) or the context is destroyed.  It
+ * waits for a call in flight on the context, like dprf_ctx_set_pdf_password.  The whole table is refused, and the
+ * previous one stays, on: an empty word, a word with a NUL byte, an Office word that is not valid UTF-8
+ * (DPRF_E_DOMAIN); n >= 2^32 or converted words of 2^32 bytes or more in all (DPRF_E_INVALID).  The message names the
+ * first offending word's index.  dprf_words_status is the host-only check of the same rules: 0 or the DPRF_E_* code
+ * per word into status[n] (may be NULL), returning the number of refused words, so a caller can drop them and keep
+ * the rest.  dprf_ctx_words returns the number of words held (0: no table). */
+int dprf_ctx_set_words(dprf_ctx *ctx, const uint8_t *blob, const uint64_t *offsets, int64_t n);
+int64_t dprf_ctx_words(const dprf_ctx *ctx);
+int dprf_words_status(const dprf_ctx *ctx, const uint8_t *blob, const uint64_t *offsets, int64_t n, int8_t *status);
+
+/* The search: a mask of npos positions, 0 <= npos <= DPRF_MAX_PW_RANGE, given and checked as dprf_search_mask's
+ * (with npos = 0 the three mask arguments may be NULL), of keyspace M = the product of the positions' symbol counts
+ * (1 for npos = 0); word_at in 0..npos says before which mask position the word is spelled: 0 prepends it, npos
+ * appends it.  Candidate i of the keyspace N * M (N words) is word i / M with mask index i % M, the mask part spelled
+ * as dprf_search_mask spells it (the last position fastest): the word is the slowest digit wherever it stands.  The
+ * bytes are the concatenation in spelling order, and the format's truncation applies to the whole candidate (PDF
+ * R2-R4 32 bytes, R5 127).
+ * Errors beyond dprf_search_mask's: DPRF_E_INVALID -- no table set, word_at outside 0..npos, or start + count above
+ * N * M (computed without wrapping); DPRF_E_PWLEN -- min(the longest converted word + the sum over the positions of
+ * the position's longest symbol, the truncation) exceeds a 64-byte slot (the message names the word).  Where the
+ * truncation is at most 64 bytes (R2-R4) a word of any length is accepted.  A refused call leaves no per-device
+ * record, and the context still serves.
+ * The device spells every candidate into a list slot (k_spell_hybrid) from the table it holds; per call only the mask
+ * table goes up, per launch only the chunk start's word index and mask digits.  hits[] relative to `start`,
+ * stop_on_first (the lowest verifying index), multi-device chunks, the cross-device stop, stats, owner mode and
+ * DPRF_FLAG_NEVER_MATCHES contexts are as dprf_search_mask's.  Long candidates stay unsupported for Agile and owner
+ * R5/R6 as above: they do not fit the slot. */
+int dprf_search_hybrid(dprf_ctx *ctx, const uint8_t *sym, const uint32_t *sym_off, const uint32_t *pos_off, int npos,
+                       int word_at, uint64_t start, uint64_t count, int stop_on_first, uint64_t *hits, int64_t cap,
+                       int64_t *nhits, dprf_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
