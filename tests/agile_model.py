@@ -105,6 +105,30 @@ def make_parts(pw, version, key_bits, spin, seed):
     return salt, cbc_encrypt(key1, salt, verifier), cbc_encrypt(key2, salt, hv)
 
 
+def plain_parts(version, seed):
+    """(salt, verifier, padded hash value): the plaintexts make_parts draws for this seed, before encryption."""
+    H = HASHES[str(version)][0]
+    rng = random.Random(seed)
+    salt = bytes(rng.getrandbits(8) for _ in range(16))
+    verifier = bytes(rng.getrandbits(8) for _ in range(16))
+    hv = H(verifier).digest()
+    return salt, verifier, hv + b"\0" * (-len(hv) % 16)
+
+
+def make_parts_from(pw, version, key_bits, spin, salt, verifier, hash_value):
+    """make_parts for given plaintexts: any 16-byte verifier and any hash value of whole blocks, encrypted under the
+    keys derived from pw -- a document whose stored hash need not be the verifier's (tests/test_verdict_compare.py)."""
+    assert len(verifier) == 16 and len(hash_value) % 16 == 0
+    key1, key2 = derive_keys(pw, str(version), key_bits, salt, spin)
+    return salt, cbc_encrypt(key1, salt, verifier), cbc_encrypt(key2, salt, hash_value)
+
+
+def stream_of(version, key_bits, spin, salt, evi, evh, name="made.docx"):
+    """The verifier stream of the three parts, as office2john prints it (the first 32 bytes of the hash value)."""
+    return "%s:$office$*%s*%d*%d*%d*%s*%s*%s" % (name, version, spin, key_bits, 16, salt.hex(), evi.hex(),
+                                                 evh.hex()[:64])
+
+
 def make_stream(pw, version, key_bits, spin, seed, name="made.docx"):
     """The verifier stream of a document protected with pw, as office2john prints it."""
     salt, evi, evh = make_parts(pw, version, key_bits, spin, seed)

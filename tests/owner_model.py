@@ -70,8 +70,10 @@ def _aes_cbc(key, iv, data):
     return b"".join(out)
 
 
+@functools.lru_cache(maxsize=None)
 def r6_hash(pw, salt, udata):
-    """ISO 32000-2 Algorithm 2.B with the owner's udata = U[0:48]."""
+    """ISO 32000-2 Algorithm 2.B with the owner's udata = U[0:48].  A pure function of three bytes objects, memoised:
+    streams that differ only in O[0:32] or O[40:48] (tests/test_verdict_compare.py) share one evaluation."""
     k = O.sha256(pw + salt + udata)
     i = 0
     while True:
@@ -92,6 +94,14 @@ def owner_verifies(stream, pw_bytes):
     if d["R"] == 5:
         return O.sha256(pw[:127] + o[32:40] + u[:48]) == o[:32]
     return r6_hash(pw, o[32:40], u[:48]) == o[:32]
+
+
+def compared_bytes(stream, pw):
+    """R3/R4: the 16 bytes the check compares with U[0:16] for the owner candidate pw -- the user check's RC4 output
+    (pyoracle intermediates [48:64]) for the 32 bytes /O decrypts to.  They do not depend on U."""
+    d = parse(stream)
+    assert 3 <= d["R"] <= 4
+    return _ctx(tuple(d["fields"])).intermediates(owner_decrypts_to(stream, pw))[48:64]
 
 
 def index_of(pw, charset):
