@@ -645,21 +645,31 @@ static int verify_odt(const orc_ctx *c, const uint8_t *pw, int len, uint8_t *int
 static const uint8_t PDF_PAD[32] = {0x28,0xBF,0x4E,0x5E,0x4E,0x75,0x8A,0x41,0x64,0x00,0x4E,0x56,0xFF,0xFA,
     0x01,0x08,0x2E,0x2E,0x00,0xB6,0xD0,0x68,0x3E,0x80,0x2F,0x0C,0xA9,0xFE,0x64,0x53,0x69,0x7A};
 
-/* pdf_compute_hardened_hash_r6 (pdf...c:226-291), ownerkey == NULL */
-static void pdf_r6_hash(const uint8_t *pw, int pwlen, const uint8_t salt[8], uint8_t out[32]) {
+/* pdf_compute_hardened_hash_r6 (pdf...c:226-291).  ulen == 0 is the reference's ownerkey == NULL; ulen > 0 is the
+ * owner form of ISO 32000-2 Algorithm 2.B: udata follows the salt in the first message and K in every period.
+ * trace (may be NULL) takes two bytes per round while rounds < cap: the block size of the K the round's periods carry
+ * (32 after SHA-256, 48 after SHA-384, 64 after SHA-512; round 0 always 32) and the round's last ciphertext byte, the
+ * one the exit rule reads.  Returns the number of rounds run. */
+static int pdf_r6_core(const uint8_t *pw, int pwlen, const uint8_t salt[8], const uint8_t *udata, int ulen,
+                       uint8_t out[32], uint8_t *trace, int cap) {
     uint8_t block[64];
     int bs = 32;
     sha256_t s;
-    sha256_init(&s); sha256_update(&s, pw, (size_t)pwlen); sha256_update(&s, salt, 8); sha256_final(&s, block);
+    sha256_init(&s); sha256_update(&s, pw, (size_t)pwlen); sha256_update(&s, salt, 8);
+    if (ulen) sha256_update(&s, udata, (size_t)ulen);
+    sha256_final(&s, block);
     size_t dlen = 0;
-    uint8_t *data = (uint8_t *)malloc((size_t)(pwlen + 64) * 64);
+    uint8_t *data = (uint8_t *)malloc((size_t)(pwlen + 64 + ulen) * 64);
     uint8_t last = 0;
-    for (int i = 0; i < 64 || i < (int)last + 32; i++) {              /* (:247) */
-        dlen = (size_t)(pwlen + bs);
+    int i;
+    for (i = 0; i < 64 || i < (int)last + 32; i++) {                  /* (:247) */
+        dlen = (size_t)(pwlen + bs + ulen);
         for (int j = 0; j < 64; j++) {                                   /* (:250-256) */
             memcpy(data + j * dlen, pw, (size_t)pwlen);
             memcpy(data + j * dlen + pwlen, block, (size_t)bs);
+            if (ulen) memcpy(data + j * dlen + pwlen + bs, udata, (size_t)ulen);
         }
+        if (trace && i < cap) trace[2 * i] = (uint8_t)bs;
         uint8_t rk[240], chain[16];
         int nr = aes_expand(block, 128, rk);                             /* (:259) */
         memcpy(chain, block + 16, 16);
@@ -677,9 +687,21 @@ static void pdf_r6_hash(const uint8_t *pw, int pwlen, const uint8_t salt[8], uin
         else if (bs == 48) orc_sha384(data, dlen * 64, block);
         else orc_sha512(data, dlen * 64, block);
         last = data[dlen * 64 - 1];
+        if (trace && i < cap) trace[2 * i + 1] = last;
     }
     free(data);
     memcpy(out, block, 32);
+    return i;
+}
+
+static void pdf_r6_hash(const uint8_t *pw, int pwlen, const uint8_t salt[8], uint8_t out[32]) {
+    pdf_r6_core(pw, pwlen, salt, NULL, 0, out, NULL, 0);
+}
+
+int orc_pdf_r6_trace(const uint8_t *pw, int len, const uint8_t salt8[8], const uint8_t *udata, int ulen,
+                     uint8_t hash32[32], uint8_t *trace, int cap) {
+    if (len < 0 || len > 176 || ulen < 0 || ulen > 48) return -1;       /* data[] of the reference, verify_pdf below */
+    return pdf_r6_core(pw, len, salt8, udata, ulen, hash32, trace, cap);
 }
 
 /* PDF: verify() pdf_password_verifier.c:64-192.  inter: R<=4 padded[32] | initial hash[16] | U'[32];
@@ -841,6 +863,49 @@ int orc_verify_list(const orc_ctx *c, const uint8_t *blob, const uint64_t *offse
         j->c = c; j->blob = blob; j->offs = offsets; j->verdicts = verdicts;
         j->start = s; j->count = per + ((uint64_t)t < rem ? 1 : 0); s += j->count;
         pthread_create(&th[t], NULL, list_worker, j);
+    }
+    for (int t = 0; t < nthreads; t++) pthread_join(th[t], NULL);
+    free(jobs); free(th);
+    return 0;
+}
+
+/* ------------------------------------------------------------------ R6 traces over a range-mode window */
+typedef struct {
+    const uint8_t *salt, *udata, *cs; int ulen, cslen, pwlen; uint64_t start, count, off;
+    uint16_t *rounds; uint8_t *final, *edge;
+} r6job_t;
+
+static void *r6_trace_worker(void *arg) {
+    r6job_t *j = (r6job_t *)arg;
+    uint8_t pw[256], hh[32], tr[2 * 256];
+    for (uint64_t k = 0; k < j->count; k++) {
+        index_to_pw(j->start + k, j->cs, j->cslen, j->pwlen, pw);
+        int n = pdf_r6_core(pw, j->pwlen, j->salt, j->udata, j->ulen, hh, tr, 256);
+        int e = 0;
+        for (int i = 64; i < n && !e; i++)                               /* i rounds done, byte i - 31: goes on by one */
+            if ((int)tr[2 * (i - 1) + 1] == i - 31) e = i;
+        j->rounds[j->off + k] = (uint16_t)n;
+        j->final[j->off + k] = tr[2 * (n - 1) + 1];
+        if (j->edge) j->edge[j->off + k] = (uint8_t)e;
+    }
+    return NULL;
+}
+
+int orc_pdf_r6_trace_range(const uint8_t salt8[8], const uint8_t *udata, int ulen, const uint8_t *cs, int cslen,
+                           int pwlen, uint64_t start, uint64_t count, int nthreads,
+                           uint16_t *rounds, uint8_t *final, uint8_t *edge) {
+    if (nthreads < 1) nthreads = 1;
+    if (pwlen < 1 || pwlen > 176 || cslen < 1 || ulen < 0 || ulen > 48) return -1;
+    if ((uint64_t)nthreads > count) nthreads = count ? (int)count : 1;
+    r6job_t *jobs = (r6job_t *)calloc((size_t)nthreads, sizeof(r6job_t));
+    pthread_t *th = (pthread_t *)calloc((size_t)nthreads, sizeof(pthread_t));
+    uint64_t per = count / (uint64_t)nthreads, rem = count % (uint64_t)nthreads, s = 0;
+    for (int t = 0; t < nthreads; t++) {
+        r6job_t *j = &jobs[t];
+        j->salt = salt8; j->udata = udata; j->ulen = ulen; j->cs = cs; j->cslen = cslen; j->pwlen = pwlen;
+        j->off = s; j->start = start + s; j->count = per + ((uint64_t)t < rem ? 1 : 0); s += j->count;
+        j->rounds = rounds; j->final = final; j->edge = edge;
+        pthread_create(&th[t], NULL, r6_trace_worker, j);
     }
     for (int t = 0; t < nthreads; t++) pthread_join(th[t], NULL);
     free(jobs); free(th);

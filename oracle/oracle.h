@@ -75,6 +75,22 @@ int orc_intermediates(const orc_ctx *ctx, const uint8_t *pw, int len, uint8_t *o
 #define ORC_NCOUNT 10
 int orc_work_counts(const orc_ctx *ctx, const uint8_t *pw, int len, uint64_t counts[ORC_NCOUNT]);
 
+/* ---- the PDF R6 hardened hash, round by round (tests/golden/make_r6_traces.py, tests/r6_plant.py) ----
+ * The hash of pw under salt8; ulen > 0 selects the owner form (ISO 32000-2 Algorithm 2.B with udata = U[0:48]: udata
+ * follows the salt in the first message and K in every period).  It does not depend on the 32 bytes a verifier
+ * compares it with.  Returns the number of rounds run (64 or more), -1 for len > 176 or ulen > 48.  trace may be NULL;
+ * otherwise round i < cap writes trace[2i] = the length of the K its periods carry (32, 48 or 64; round 0: 32) and
+ * trace[2i+1] = its last ciphertext byte.  The loop ends after n rounds when n >= 64 and trace[2(n-1)+1] <= n - 32. */
+int orc_pdf_r6_trace(const uint8_t *pw, int len, const uint8_t salt8[8], const uint8_t *udata, int ulen,
+                     uint8_t hash32[32], uint8_t *trace, int cap);
+
+/* The same over [start, start+count) of charset^pwlen (orc_search_range's order), threaded.  Per index: rounds[k] =
+ * the round count, final[k] = the last round's byte, and (edge may be NULL) edge[k] = the smallest n >= 64 at which
+ * the byte after n rounds was exactly n - 31, so that the candidate went on by exactly one round's margin; 0: none. */
+int orc_pdf_r6_trace_range(const uint8_t salt8[8], const uint8_t *udata, int ulen, const uint8_t *charset, int cslen,
+                           int pwlen, uint64_t start, uint64_t count, int nthreads,
+                           uint16_t *rounds, uint8_t *final, uint8_t *edge);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,7 +57,13 @@ def lib():
                                       ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int8)]
         L.orc_intermediates.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.orc_work_counts.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
-        _ = u8p
+        L.orc_pdf_r6_trace.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int,
+                                       ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]
+        L.orc_pdf_r6_trace.restype = ctypes.c_int
+        L.orc_pdf_r6_trace_range.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
+                                             ctypes.c_int, ctypes.POINTER(ctypes.c_uint16), u8p, u8p]
+        L.orc_pdf_r6_trace_range.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -170,6 +176,36 @@ class Ctx:
         v = (ctypes.c_int8 * max(1, len(bs)))()
         lib().orc_verify_list(self.h, blob, o, len(bs), nthreads or min(8, os.cpu_count() or 1), v)
         return list(v[:len(bs)])
+
+
+R6_TRACE_CAP = 256
+
+
+def pdf_r6_trace(pw, salt8, udata=b""):
+    """The R6 hardened hash of pw under salt8 (udata = U[0:48]: the owner form), round by round:
+    (hash32, [(bs, last byte) per round]); len(trace) is the round count.  ValueError past 176 bytes."""
+    pw = pw.encode() if isinstance(pw, str) else bytes(pw)
+    assert len(salt8) == 8 and len(udata) in (0, 48)
+    hh = ctypes.create_string_buffer(32)
+    tr = ctypes.create_string_buffer(2 * R6_TRACE_CAP)
+    n = lib().orc_pdf_r6_trace(pw, len(pw), bytes(salt8), bytes(udata), len(udata), hh, tr, R6_TRACE_CAP)
+    if n < 0:
+        raise ValueError("oracle: R6 candidate of %d bytes is outside the parity domain" % len(pw))
+    assert 64 <= n <= R6_TRACE_CAP
+    return hh.raw, [(tr.raw[2 * i], tr.raw[2 * i + 1]) for i in range(n)]
+
+
+def pdf_r6_trace_range(salt8, charset, pwlen, start, count, udata=b"", nthreads=None):
+    """Per index of [start, start+count) of charset^pwlen: (rounds, final byte, edge) lists; oracle.h names edge."""
+    cs = charset.encode() if isinstance(charset, str) else bytes(charset)
+    rounds = (ctypes.c_uint16 * count)()
+    final = (ctypes.c_uint8 * count)()
+    edge = (ctypes.c_uint8 * count)()
+    rc = lib().orc_pdf_r6_trace_range(bytes(salt8), bytes(udata), len(udata), cs, len(cs), pwlen, start, count,
+                                      nthreads or min(8, os.cpu_count() or 1), rounds, final, edge)
+    if rc != 0:
+        raise ValueError("oracle pdf_r6_trace_range error %d" % rc)
+    return list(rounds), list(final), list(edge)
 
 
 def index_to_password(idx, charset, pwlen):

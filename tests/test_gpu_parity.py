@@ -229,7 +229,12 @@ def test_random_documents_vs_oracle(dprf, oracle, kind, kw, n, seed):
 @pytest.mark.parametrize("name", ["pdf_synth_r2_key", "pdf_synth_r3_l128_abc", "pdf_synth_r5_cat", "pdf_synth_r6_ox",
                                   "odt_synth_std_zq", "office_synth_ok"])
 def test_ragged_lengths_and_limits(dprf, oracle, streams, name):
-    """Lengths 0..64 in one payload (32/33 around the PDF truncation, 55/56 around the SHA block edge)."""
+    """Lengths 0..64 in one payload (32/33 around the PDF truncation, 55/56 around the SHA block edge).
+
+    Only the document's password can hit, so the other candidates check that every length is accepted, framed and
+    rejected -- a kernel that computed the wrong thing at one of those lengths would reject them just the same.  What
+    is computed at each length is checked where a password of that length is planted: tests/test_r6_traces.py (R6,
+    every length) and tests/test_dense_hits.py (every lane and slot of a launch)."""
     rng = random.Random(11)
     lens = list(range(0, 65)) if not name.startswith("office") else [1, 2, 19, 20, 27, 28, 31, 32]
     words = ["".join(rng.choice(ALNUM) for _ in range(k)) for k in lens] + [streams[name]["password"]]
