@@ -261,6 +261,29 @@ class Context:
             _check(n)
         return [arr[k].as_dict() for k in range(min(n, 64))]
 
+    def _call(self, export, args, stop_on_first, cap, start=0):
+        """One search / verify export: `args` are what it takes between the context and stop_on_first.  Returns (hit
+        indices with `start` added (at most cap), total hits, stats dict)."""
+        hits = (ctypes.c_uint64 * max(1, cap))()
+        nh = ctypes.c_int64()
+        st = Stats()
+        _check(export(self._h, *args, 1 if stop_on_first else 0, hits, cap, ctypes.byref(nh), ctypes.byref(st)))
+        return [start + h for h in hits[:min(nh.value, cap)]], nh.value, st.as_dict()
+
+    @staticmethod
+    def _symbols(positions):
+        """One sequence of symbols per position (a str: each character a symbol, its UTF-8 bytes; bytes: byte symbols)
+        as the exports take them: (symbol blob, symbol offsets, per-position offsets into those, positions)."""
+        syms, poffs = [], [0]
+        for pos in positions:
+            syms.extend([ch.encode("utf-8") for ch in pos] if isinstance(pos, str) else [bytes([b]) for b in pos])
+            poffs.append(len(syms))
+        offs = [0]
+        for b in syms:
+            offs.append(offs[-1] + len(b))
+        return (b"".join(syms), (ctypes.c_uint32 * len(offs))(*offs), (ctypes.c_uint32 * len(poffs))(*poffs),
+                len(poffs) - 1)
+
     def search_range(self, charset, pwlen, start, count, stop_on_first=False, cap=1 << 16):
         """Verify keyspace indices [start, start+count) of charset^pwlen (itertools.product order).
         Returns (sorted hit indices (at most cap), total hits, stats dict).  The library's symbols are bytes: a str
@@ -272,12 +295,7 @@ class Context:
                                        "(search_symbols enumerates characters)" % charset)
         start, count = _check_window(start, count)
         cs = _to_bytes(charset)
-        hits = (ctypes.c_uint64 * max(1, cap))()
-        nh = ctypes.c_int64()
-        st = Stats()
-        _check(lib().dprf_search_range(self._h, cs, len(cs), int(pwlen), start, count,
-                                       1 if stop_on_first else 0, hits, cap, ctypes.byref(nh), ctypes.byref(st)))
-        return list(hits[:min(nh.value, cap)]), nh.value, st.as_dict()
+        return self._call(lib().dprf_search_range, (cs, len(cs), int(pwlen), start, count), stop_on_first, cap)
 
     def search_symbols(self, charset, pwlen, start, count, stop_on_first=False, cap=1 << 16):
         """Verify keyspace indices [start, start+count) of charset^pwlen over the CHARACTERS of a str charset (each
@@ -285,17 +303,9 @@ class Context:
         include/dprf.h dprf_search_symbols).  Returns (sorted hit indices -- keyspace indices, like search_range's --,
         total hits, stats dict).  DprfError(E_PWLEN) when a candidate could exceed a 64-byte list slot."""
         start, count = _check_window(start, count)
-        syms = [ch.encode("utf-8") for ch in charset] if isinstance(charset, str) else [bytes([b]) for b in charset]
-        offs = [0]
-        for b in syms:
-            offs.append(offs[-1] + len(b))
-        so = (ctypes.c_uint32 * len(offs))(*offs)
-        hits = (ctypes.c_uint64 * max(1, cap))()
-        nh = ctypes.c_int64()
-        st = Stats()
-        _check(lib().dprf_search_symbols(self._h, b"".join(syms), so, len(syms), int(pwlen), start, count,
-                                         1 if stop_on_first else 0, hits, cap, ctypes.byref(nh), ctypes.byref(st)))
-        return [start + h for h in hits[:min(nh.value, cap)]], nh.value, st.as_dict()
+        blob, so, _, _ = self._symbols([charset])
+        return self._call(lib().dprf_search_symbols, (blob, so, len(so) - 1, int(pwlen), start, count), stop_on_first,
+                          cap, start)
 
     def search_mask(self, positions, start, count, stop_on_first=False, cap=1 << 16):
         """Verify keyspace indices [start, start+count) of a mask: `positions` is one sequence of symbols per position
@@ -303,21 +313,7 @@ class Context:
         symbols), enumerated in itertools.product order and spelled on the device (ABI 8, include/dprf.h
         dprf_search_mask).  Returns (sorted hit indices -- keyspace indices --, total hits, stats dict)."""
         start, count = _check_window(start, count)
-        syms, poffs = [], [0]
-        for pos in positions:
-            syms.extend([ch.encode("utf-8") for ch in pos] if isinstance(pos, str) else [bytes([b]) for b in pos])
-            poffs.append(len(syms))
-        offs = [0]
-        for b in syms:
-            offs.append(offs[-1] + len(b))
-        so = (ctypes.c_uint32 * len(offs))(*offs)
-        po = (ctypes.c_uint32 * len(poffs))(*poffs)
-        hits = (ctypes.c_uint64 * max(1, cap))()
-        nh = ctypes.c_int64()
-        st = Stats()
-        _check(lib().dprf_search_mask(self._h, b"".join(syms), so, po, len(poffs) - 1, start, count,
-                                      1 if stop_on_first else 0, hits, cap, ctypes.byref(nh), ctypes.byref(st)))
-        return [start + h for h in hits[:min(nh.value, cap)]], nh.value, st.as_dict()
+        return self._call(lib().dprf_search_mask, self._symbols(positions) + (start, count), stop_on_first, cap, start)
 
     @staticmethod
     def _word_blob(words):
@@ -364,21 +360,8 @@ class Context:
         i // M with mask index i % M, spelled on the device (include/dprf.h dprf_search_hybrid).  Returns (sorted hit
         indices -- keyspace indices --, total hits, stats dict)."""
         start, count = _check_window(start, count)
-        syms, poffs = [], [0]
-        for pos in positions:
-            syms.extend([ch.encode("utf-8") for ch in pos] if isinstance(pos, str) else [bytes([b]) for b in pos])
-            poffs.append(len(syms))
-        offs = [0]
-        for b in syms:
-            offs.append(offs[-1] + len(b))
-        so = (ctypes.c_uint32 * len(offs))(*offs)
-        po = (ctypes.c_uint32 * len(poffs))(*poffs)
-        hits = (ctypes.c_uint64 * max(1, cap))()
-        nh = ctypes.c_int64()
-        st = Stats()
-        _check(lib().dprf_search_hybrid(self._h, b"".join(syms), so, po, len(poffs) - 1, int(word_at), start, count,
-                                        1 if stop_on_first else 0, hits, cap, ctypes.byref(nh), ctypes.byref(st)))
-        return [start + h for h in hits[:min(nh.value, cap)]], nh.value, st.as_dict()
+        return self._call(lib().dprf_search_hybrid, self._symbols(positions) + (int(word_at), start, count),
+                          stop_on_first, cap, start)
 
     def verify_blob(self, blob, offsets, stop_on_first=False, cap=1 << 16):
         """verify_list without per-candidate Python work: candidate k is blob[offsets[k]:offsets[k+1]]
@@ -388,12 +371,8 @@ class Context:
         n = len(offs) - 1
         if n < 0:
             raise ValueError("offsets needs n+1 entries")
-        hits = (ctypes.c_uint64 * max(1, cap))()
-        nh = ctypes.c_int64()
-        st = Stats()
-        _check(lib().dprf_verify_list(self._h, bytes(blob), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
-                                      n, 1 if stop_on_first else 0, hits, cap, ctypes.byref(nh), ctypes.byref(st)))
-        return list(hits[:min(nh.value, cap)]), nh.value, st.as_dict()
+        return self._call(lib().dprf_verify_list,
+                          (bytes(blob), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n), stop_on_first, cap)
 
     def list_status(self, blob, offsets):
         """Per-candidate validity for this format without device work: a numpy int8 array, 0 = valid,
@@ -415,11 +394,5 @@ class Context:
         offs = [0]
         for b in bs:
             offs.append(offs[-1] + len(b))
-        blob = b"".join(bs)
-        o = (ctypes.c_uint64 * len(offs))(*offs)
-        hits = (ctypes.c_uint64 * max(1, cap))()
-        nh = ctypes.c_int64()
-        st = Stats()
-        _check(lib().dprf_verify_list(self._h, blob, o, len(bs), 1 if stop_on_first else 0, hits, cap,
-                                      ctypes.byref(nh), ctypes.byref(st)))
-        return list(hits[:min(nh.value, cap)]), nh.value, st.as_dict()
+        return self._call(lib().dprf_verify_list, (b"".join(bs), (ctypes.c_uint64 * len(offs))(*offs), len(bs)),
+                          stop_on_first, cap)

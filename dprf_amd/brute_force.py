@@ -279,6 +279,41 @@ def search_round(ctx, charset, pwlen, start, count, stop_on_first=True):
     return found, total
 
 
+def _resumable_search(input_data, cp, devices, owner, begin):
+    """What range, mask and hybrid mode share: answer from a finished checkpoint without a context; else one context
+    (closed at the end), "_dummy" first when the search starts at index 0 -- as the reference queues it beside the
+    keyspace (brute_force.py:76) -- and the rounds from the checkpoint's cursor.  begin(ctx) does what the mode needs
+    of the context before that (hybrid mode filters its words) and returns run(rounds, done, t0) -> (found, password),
+    which searches from index `done` with rounds(done, space, search, spell), :func:`_rounds` of this search."""
+    done, prior = cp.load()
+    if prior is not None:
+        print("Checkpoint: search already finished, password '%s'" % prior)
+        return 1, prior
+    ctx = _context(input_data, devices, owner=True) if owner else _context(input_data, devices)
+    t0 = time.time()
+    tried = 0
+    try:
+        run = begin(ctx)
+        if done == 0:
+            hits, _, _ = ctx.verify_list([DUMMY], stop_on_first=True, cap=1)
+            tried += 1
+            if hits:
+                cp.save(0, DUMMY)
+                _report(DUMMY, tried, t0, owner)
+                return 1, DUMMY
+        else:
+            print("Checkpoint: resuming at index %d" % done)
+        return run(lambda start, space, search, spell: _rounds(ctx, cp, start, space, tried, t0, search, spell, owner),
+                   done, t0)
+    finally:
+        ctx.close()
+
+
+def _plain(space, search, spell):
+    """run() of a search that is its rounds and nothing else (_resumable_search)."""
+    return lambda rounds, done, t0: rounds(done, space, search, spell)
+
+
 def init_rangebased_brute_force(input_data, password_range, charset=LOWERCASE, devices=None, checkpoint=None,
                                 owner=False):
     """charset^password_range in product order, plus "_dummy" (brute_force.py:60-79, :199-219).
@@ -289,28 +324,11 @@ def init_rangebased_brute_force(input_data, password_range, charset=LOWERCASE, d
     (:class:`Checkpoint`).  charset: see check_charset (raises before any device work)."""
     check_charset(charset)
     cp = Checkpoint(checkpoint, input_data, charset, password_range, target="owner" if owner else "user")
-    done, prior = cp.load()
-    if prior is not None:
-        print("Checkpoint: search already finished, password '%s'" % prior)
-        return 1, prior
-    ctx = _context(input_data, devices, owner=True) if owner else _context(input_data, devices)
-    t0 = time.time()
-    tried = 0
-    try:
-        if done == 0:
-            hits, _, _ = ctx.verify_list([DUMMY], stop_on_first=True, cap=1)
-            tried += 1
-            if hits:
-                cp.save(0, DUMMY)
-                _report(DUMMY, tried, t0, owner)
-                return 1, DUMMY
-        else:
-            print("Checkpoint: resuming at index %d" % done)
-        return _rounds(ctx, cp, done, len(charset) ** password_range, tried, t0,
-                       lambda start, n: search_round(ctx, charset, password_range, start, n),
-                       lambda idx: _index_to_password(idx, charset, password_range), owner)
-    finally:
-        ctx.close()
+    return _resumable_search(
+        input_data, cp, devices, owner,
+        lambda ctx: _plain(len(charset) ** password_range,
+                           lambda start, n: search_round(ctx, charset, password_range, start, n),
+                           lambda idx: _index_to_password(idx, charset, password_range)))
 
 
 def _rounds(ctx, cp, done, space, tried, t0, search, spell, owner=False):
@@ -343,31 +361,15 @@ def init_mask_brute_force(input_data, mask, custom_charsets=(), devices=None, ch
     positions = masks.parse_mask(mask, custom_charsets)
     space = masks.space(positions)
     cp = Checkpoint(checkpoint, input_data, mask=mask, custom=custom_charsets, target="owner" if owner else "user")
-    done, prior = cp.load()
-    if prior is not None:
-        print("Checkpoint: search already finished, password '%s'" % prior)
-        return 1, prior
-    ctx = _context(input_data, devices, owner=True) if owner else _context(input_data, devices)
-    t0 = time.time()
-    tried = 0
-    try:
-        if done == 0:
-            hits, _, _ = ctx.verify_list([DUMMY], stop_on_first=True, cap=1)
-            tried += 1
-            if hits:
-                cp.save(0, DUMMY)
-                _report(DUMMY, tried, t0, owner)
-                return 1, DUMMY
-        else:
-            print("Checkpoint: resuming at index %d" % done)
 
+    def begin(ctx):
         def search(start, n):
             hits, _, st = ctx.search_mask(positions, start, n, stop_on_first=True, cap=1)
             return (hits[0] if hits else None), st
 
-        return _rounds(ctx, cp, done, space, tried, t0, search, lambda idx: masks.word(positions, idx), owner)
-    finally:
-        ctx.close()
+        return _plain(space, search, lambda idx: masks.word(positions, idx))
+
+    return _resumable_search(input_data, cp, devices, owner, begin)
 
 
 def wordlist_key(words):
@@ -409,14 +411,9 @@ def init_hybrid_brute_force(input_data, wordlist, mask="?w", custom_charsets=(),
     words = hybrid.read_wordlist(wordlist) if isinstance(wordlist, str) else [hybrid._bytes(w) for w in wordlist]
     cp = Checkpoint(checkpoint, input_data, mask=mask, custom=custom_charsets, target="owner" if owner else "user",
                     wordlist=wordlist_key(words))
-    done, prior = cp.load()
-    if prior is not None:
-        print("Checkpoint: search already finished, password '%s'" % prior)
-        return 1, prior
-    ctx = _context(input_data, devices, owner=True) if owner else _context(input_data, devices)
-    t0 = time.time()
-    tried = 0
-    try:
+
+    def begin(ctx):
+        nonlocal words
         status = ctx.words_status(words)
         bad = [k for k in range(len(words)) if status[k] != 0]
         if bad:
@@ -430,41 +427,34 @@ def init_hybrid_brute_force(input_data, wordlist, mask="?w", custom_charsets=(),
                 len(late), "; they are verified as a list at the end" if not positions else ""))
             words = [w for w, ok in zip(words, fit) if ok]
         space = hybrid.space(len(words), positions)
-        if done == 0:
-            hits, _, _ = ctx.verify_list([DUMMY], stop_on_first=True, cap=1)
-            tried += 1
-            if hits:
-                cp.save(0, DUMMY)
-                _report(DUMMY, tried, t0, owner)
-                return 1, DUMMY
-        else:
-            print("Checkpoint: resuming at index %d" % done)
-        if words:
-            ctx.set_words(words)
 
         def search(start, n):
             hits, _, st = ctx.search_hybrid(positions, word_at, start, n, stop_on_first=True, cap=1)
             return (hits[0] if hits else None), st
 
-        if positions or not late:
-            return _rounds(ctx, cp, done, space, tried, t0, search,
-                           lambda idx: hybrid.text(hybrid.candidate(words, positions, word_at, idx)), owner)
-        # the bare word: the table first, then the words over a slot's length as one list (indices space ..)
-        found, pw = _rounds(ctx, cp, min(done, space), space, tried, t0, search,
-                            lambda idx: hybrid.text(words[idx]), owner)
-        if found or done >= space + len(late):
-            return found, pw
-        ok = ctx.list_status(b"".join(late), [0] + [sum(map(len, late[:k + 1])) for k in range(len(late))])
-        kept = [w for k, w in enumerate(late) if ok[k] == 0]
-        if len(kept) < len(late):
-            print("Dropped %d long words this format does not take in list mode" % (len(late) - len(kept)))
-        hits, _, _ = ctx.verify_list(kept, stop_on_first=True, cap=1) if kept else ([], 0, None)
-        found_pw = hybrid.text(kept[hits[0]]) if hits else None
-        cp.save(space + len(late), found_pw)
-        _report(found_pw, len(kept), t0, owner)
-        return (1, found_pw) if found_pw is not None else (0, DEFAULT_PASSWORD)
-    finally:
-        ctx.close()
+        def run(rounds, done, t0):
+            if words:
+                ctx.set_words(words)
+            if positions or not late:
+                return rounds(done, space, search,
+                              lambda idx: hybrid.text(hybrid.candidate(words, positions, word_at, idx)))
+            # the bare word: the table first, then the words over a slot's length as one list (indices space ..)
+            found, pw = rounds(min(done, space), space, search, lambda idx: hybrid.text(words[idx]))
+            if found or done >= space + len(late):
+                return found, pw
+            ok = ctx.list_status(b"".join(late), [0] + [sum(map(len, late[:k + 1])) for k in range(len(late))])
+            kept = [w for k, w in enumerate(late) if ok[k] == 0]
+            if len(kept) < len(late):
+                print("Dropped %d long words this format does not take in list mode" % (len(late) - len(kept)))
+            hits, _, _ = ctx.verify_list(kept, stop_on_first=True, cap=1) if kept else ([], 0, None)
+            found_pw = hybrid.text(kept[hits[0]]) if hits else None
+            cp.save(space + len(late), found_pw)
+            _report(found_pw, len(kept), t0, owner)
+            return (1, found_pw) if found_pw is not None else (0, DEFAULT_PASSWORD)
+
+        return run
+
+    return _resumable_search(input_data, cp, devices, owner, begin)
 
 
 def init_listbased_brute_force(input_data, passwords, devices=None, owner=False):
