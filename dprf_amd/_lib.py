@@ -17,6 +17,7 @@ E_INVALID, E_DOMAIN, E_HIP, E_NODEVICE, E_PWLEN, E_CHARSET = -1, -2, -3, -4, -5,
 FLAG_NEVER_MATCHES, FLAG_REF_NONDETERMINISTIC = 1, 2
 MAX_PW, MAX_PW_RANGE, MAX_PW_R6 = 131071, 32, 176
 MAX_MASK_SYMBOLS = 2048
+MAX_RULES, MAX_RULE_FNS, MAX_RULE_WORDS, MAX_SPELL = 1 << 20, 32, 1 << 22, 1 << 20
 PDF_USER, PDF_OWNER = 0, 1
 _PDF_PASSWORDS = {"user": PDF_USER, "owner": PDF_OWNER}
 
@@ -25,7 +26,7 @@ EXPORTS = ["dprf_abi_version", "dprf_last_error", "dprf_device_count", "dprf_dev
            "dprf_ctx_devices", "dprf_search_range", "dprf_verify_list", "dprf_list_status", "dprf_build_id",
            "dprf_plan_chunk", "dprf_ctx_last_call_devices", "dprf_search_symbols", "dprf_search_mask",
            "dprf_ctx_set_pdf_password", "dprf_ctx_pdf_password", "dprf_ctx_set_words", "dprf_ctx_words",
-           "dprf_words_status", "dprf_search_hybrid"]
+           "dprf_words_status", "dprf_search_hybrid", "dprf_search_rules", "dprf_spell_rules"]
 
 
 class DprfError(RuntimeError):
@@ -129,6 +130,15 @@ def lib():
                                              ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64,
                                              ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Stats)]
             L.dprf_search_hybrid.restype = ctypes.c_int
+            L.dprf_search_rules.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+                                            ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64, ctypes.c_uint64,
+                                            ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Stats)]
+            L.dprf_search_rules.restype = ctypes.c_int
+            L.dprf_spell_rules.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64, ctypes.c_uint64,
+                                           ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+            L.dprf_spell_rules.restype = ctypes.c_int
             if L.dprf_abi_version() != ABI_VERSION:
                 raise ImportError("libdprf.so ABI %d != %d" % (L.dprf_abi_version(), ABI_VERSION))
             _lib = L
@@ -362,6 +372,52 @@ class Context:
         start, count = _check_window(start, count)
         return self._call(lib().dprf_search_hybrid, self._symbols(positions) + (int(word_at), start, count),
                           stop_on_first, cap, start)
+
+    @staticmethod
+    def _rule_table(rules):
+        """`rules` as the exports take it: a list of parsed rules (rules.parse_rule) or the encoded pair (fns,
+        rule_off) of rules.encode -> (keep-alive arrays, fns pointer, rule_off pointer, number of rules)."""
+        import numpy as np
+        from . import rules as rulemod
+        if isinstance(rules, tuple) and len(rules) == 2 and all(isinstance(x, np.ndarray) for x in rules):
+            fns, off = rules
+        else:
+            fns, off = rulemod.encode(list(rules))
+        fns = np.ascontiguousarray(fns, dtype=np.uint32)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        if fns.size == 0:
+            fns = np.zeros(1, dtype=np.uint32)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        return (fns, off), fns.ctypes.data_as(u32p), off.ctypes.data_as(u32p), len(off) - 1
+
+    def search_rules(self, rules, start, count, stop_on_first=False, cap=1 << 16):
+        """Verify keyspace indices [start, start+count) of words x rules: index i is rule i % R applied to word
+        i // R of the context's table, on the device (include/dprf.h dprf_search_rules).  `rules`: a list of parsed
+        rules (dprf_amd.rules) or the pair rules.encode returns.  Returns (sorted hit indices -- keyspace indices --,
+        total hits, stats dict)."""
+        start, count = _check_window(start, count)
+        keep, fns, off, n = self._rule_table(rules)
+        return self._call(lib().dprf_search_rules, (fns, off, n, start, count), stop_on_first, cap, start)
+
+    def spell_rules_raw(self, rules, start, count):
+        """The candidates [start, start+count) of words x rules as the device spells them, without per-candidate
+        Python work: (slots, lens), numpy uint8 arrays of shape (count, 64) and (count,) -- the zero-padded slot bytes,
+        exactly what search_rules would verify (after the format's cut; Office: UTF-16LE), and their byte lengths.  No
+        verification runs (include/dprf.h dprf_spell_rules; count <= 2^20)."""
+        import numpy as np
+        start, count = _check_window(start, count)
+        keep, fns, off, n = self._rule_table(rules)
+        room = max(1, min(count, MAX_SPELL))              # the library refuses a larger count before it writes
+        slots = np.zeros((room, 64), dtype=np.uint8)
+        lens = np.zeros(room, dtype=np.uint8)
+        _check(lib().dprf_spell_rules(self._h, fns, off, n, start, count, slots.ctypes.data, lens.ctypes.data))
+        return slots[:count], lens[:count]
+
+    def spell_rules(self, rules, start, count):
+        """spell_rules_raw as a list of bytes, one candidate each."""
+        slots, lens = self.spell_rules_raw(rules, start, count)
+        raw = slots.tobytes()
+        return [raw[64 * k:64 * k + int(lens[k])] for k in range(len(lens))]
 
     def verify_blob(self, blob, offsets, stop_on_first=False, cap=1 << 16):
         """verify_list without per-candidate Python work: candidate k is blob[offsets[k]:offsets[k+1]]

@@ -27,6 +27,9 @@ candidates go to libdprf.so in batches, one candidate per GPU lane.  Differences
   (:mod:`dprf_amd.mask`) instead of ``charset^N`` -- :func:`init_mask_brute_force`.
 * hybrid mode (an extension; ``wordlist``, ``--wordlist``): every word of a wordlist with a mask around it, the mask
   naming the word's place with ``?w`` (:mod:`dprf_amd.hybrid`) -- :func:`init_hybrid_brute_force`.
+* rule mode (an extension; ``rules``, ``--rules``): every word of a wordlist under every rule of one or two rule files
+  (:mod:`dprf_amd.rules`: "c $1", "sa@ so0"), applied on the device -- :func:`init_rules_brute_force`; ``--stdout``
+  prints the candidates instead of verifying them.
 
 The reference's four worker processes on one queue (:70-73, :92-95) are inside libdprf.so: one context
 spans the devices, and every search call fans out over them (one worker thread + HIP stream per GPU on a
@@ -42,6 +45,7 @@ import time
 from . import _lib
 from . import hybrid
 from . import mask as masks
+from . import rules as rulemod
 
 LOWERCASE = "abcdefghijklmnopqrstuvwxyz"
 ALNUM = LOWERCASE + LOWERCASE.upper() + "0123456789"   # the configs' "alnum" order: a-z A-Z 0-9
@@ -59,8 +63,14 @@ _HUGE = 1 << 62
 
 
 def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, checkpoint=None, mask=None,
-         custom_charsets=(), owner=False, wordlist=None):
+         custom_charsets=(), owner=False, wordlist=None, rules=None):
     # The common entry point (brute_force.py:39-57)
+    if rules is not None:
+        # rule mode: a wordlist and nothing else beside the rules
+        if wordlist is None:
+            raise ValueError('--rules needs a --wordlist: rules are applied to its words.')
+        if mask not in (None, "?w"):
+            raise ValueError('--rules applies to the bare words: give no --mask (or "?w") with it.')
     if wordlist is not None:
         # hybrid mode: refused before any device work when it is combined with another candidate source, or when the
         # mask has no place for the word
@@ -85,6 +95,9 @@ def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, che
     print("Initializing brute-force.")
 
     try:
+        if rules is not None:
+            return init_rules_brute_force(input_data, wordlist, rules, devices=devices, checkpoint=checkpoint,
+                                          owner=owner)
         if wordlist is not None:
             return init_hybrid_brute_force(input_data, wordlist, mask, custom_charsets=custom_charsets,
                                            devices=devices, checkpoint=checkpoint, owner=owner)
@@ -134,10 +147,12 @@ class Checkpoint:
     search's key carries "target": "owner"; a user search's key is as it always was, and a file without a target is
     a user search's, so neither loads the other's file either.  A hybrid search (wordlist: the SHA-256 of its words
     and their number) keeps its mask under a name of its own beside them, so it loads no mask search's file, no mask
-    search loads its file, and a changed wordlist is refused."""
+    search loads its file, and a changed wordlist is refused.  A rule search (rules: the SHA-256 of its encoded rules
+    and their number) adds those to the hybrid key of the bare word, so a changed rule file is refused like a changed
+    wordlist and neither search loads the other's file."""
 
     def __init__(self, path, input_data, charset=None, pwlen=None, mask=None, custom=(), target="user",
-                 wordlist=None):
+                 wordlist=None, rules=None):
         import hashlib
         self.path = path
         self.target = target
@@ -145,6 +160,8 @@ class Checkpoint:
         if wordlist is not None:
             self.key.update(hybrid_mask=mask, custom=[c or "" for c in custom], wordlist_sha256=wordlist[0],
                             words=int(wordlist[1]))
+            if rules is not None:
+                self.key.update(rules_sha256=rules[0], rules=int(rules[1]))
         elif mask is None:
             self.key.update(charset=charset, pwlen=int(pwlen))
         else:
@@ -160,7 +177,8 @@ class Checkpoint:
             return 0, None
         with open(self.path) as f:
             d = json.load(f)
-        if any(d.get(k) != v for k, v in self.key.items()) or d.get("target", "user") != self.target:
+        if (any(d.get(k) != v for k, v in self.key.items()) or d.get("target", "user") != self.target
+                or ("rules_sha256" in d) != ("rules_sha256" in self.key)):
             raise ValueError("checkpoint %s belongs to a different search" % self.path)
         return int(d["next_index"]), d.get("found")
 
@@ -457,6 +475,135 @@ def init_hybrid_brute_force(input_data, wordlist, mask="?w", custom_charsets=(),
     return _resumable_search(input_data, cp, devices, owner, begin)
 
 
+def rules_key(rules):
+    """What a rule checkpoint records of its rules: (SHA-256 over their encoded form -- the function words, then the
+    offsets --, their number)."""
+    import hashlib
+    fns, off = rulemod.encode(rules)
+    return hashlib.sha256(fns.astype("<u4").tobytes() + off.astype("<u4").tobytes()).hexdigest(), len(rules)
+
+
+def load_rules(rules):
+    """The rules of a rule search: a rule file's path, a list of one or two paths (two files are multiplied with
+    rules.product, the first file slowest), or a list of parsed rules.  Prints what was skipped or dropped."""
+    if isinstance(rules, str):
+        rules = [rules]
+    rules = list(rules)
+    if not all(isinstance(r, str) for r in rules):
+        return [tuple(r) for r in rules]
+    if not 1 <= len(rules) <= 2:
+        raise ValueError("--rules may be given once or twice (two files are multiplied)")
+    sets = []
+    for path in rules:
+        got, skipped = rulemod.read_rules(path)
+        if skipped:
+            print("Skipped %d lines of %s with functions outside the rule language" % (skipped, path))
+        sets.append(got)
+    if len(sets) == 1:
+        return sets[0]
+    got, dropped = rulemod.product(sets[0], sets[1])
+    if dropped:
+        print("Dropped %d products of more than %d functions" % (dropped, rulemod.MAX_RULE_FNS))
+    return got
+
+
+def _rule_words(ctx, input_data, words, rules):
+    """The words and rules a rule search keeps: words no candidate can contain and words over 64 converted bytes are
+    dropped (rules do not apply to them), and for Office so are rules with a unit over 0x7F.  Prints each count."""
+    office = input_data[0] == "office"
+    status = ctx.words_status(words)
+    bad = [k for k in range(len(words)) if status[k] != 0]
+    if bad:
+        print("Dropped %d words no candidate can contain (empty, a NUL byte, or for Office invalid UTF-8), the "
+              "first is word %d" % (len(bad), bad[0] + 1))
+        words = [w for k, w in enumerate(words) if status[k] == 0]
+    wide = (lambda b: len(b.decode("utf-8").encode("utf-16-le"))) if office else len
+    late = sum(1 for w in words if wide(w) > 64)
+    if late:
+        print("Dropped %d words too long for a 64-byte candidate: rules do not apply to them" % late)
+        words = [w for w in words if wide(w) <= 64]
+    if office:
+        def ascii_units(rule):
+            return all(v < 0x80 for fn, a, b in rule for kind, v in zip(rulemod.SIGNATURE[fn], (a, b)) if kind in "XY")
+        kept = [r for r in rules if ascii_units(r)]
+        if len(kept) < len(rules):
+            print("Dropped %d rules with a unit over 0x7F (Office takes the units 0x01..0x7F)" % (len(rules) - len(kept)))
+            rules = kept
+    return words, rules, office
+
+
+def rule_text(candidate, office=False):
+    """A rule candidate's bytes as the str the CLI reports: UTF-8 with undecodable bytes as surrogate escapes; for
+    Office the UTF-16LE units, a lone surrogate staying one."""
+    if office:
+        return bytes(candidate).decode("utf-16-le", "surrogatepass")
+    return hybrid.text(candidate)
+
+
+def init_rules_brute_force(input_data, wordlist, rules, devices=None, checkpoint=None, owner=False):
+    """Every word of a wordlist under every rule (dprf_amd.rules), words in file order, per word the rules in file
+    order, plus "_dummy" first as in range mode: the same rounds as hybrid mode, one ctx.search_rules call each with
+    stop_on_first, so the lowest keyspace index that verifies wins.  wordlist: a file path, or a sequence of bytes
+    words; rules: see :func:`load_rules`.  The word table goes to the devices once and the rules are applied there.
+    Words over 64 converted bytes are dropped and counted.  checkpoint: keyed by the wordlist's SHA-256 and word
+    count and by the encoded rules' SHA-256 and their number."""
+    words = hybrid.read_wordlist(wordlist) if isinstance(wordlist, str) else [hybrid._bytes(w) for w in wordlist]
+    rules = load_rules(rules)
+    if not rules:
+        raise ValueError("no rule of the rule language in the rule files")
+    cp = Checkpoint(checkpoint, input_data, mask="?w", custom=(), target="owner" if owner else "user",
+                    wordlist=wordlist_key(words), rules=rules_key(rules))
+
+    def begin(ctx):
+        kept, used, office = _rule_words(ctx, input_data, words, rules)
+        table = rulemod.encode(used)
+        space = rulemod.space(len(kept), len(used))
+
+        def search(start, n):
+            hits, _, st = ctx.search_rules(table, start, n, stop_on_first=True, cap=1)
+            return (hits[0] if hits else None), st
+
+        def run(rounds, done, t0):
+            if kept:
+                ctx.set_words(kept)
+            return rounds(done, space, search, lambda idx: rule_text(rulemod.candidate(kept, used, idx, office), office))
+
+        return run
+
+    return _resumable_search(input_data, cp, devices, owner, begin)
+
+
+def print_rule_candidates(input_data, wordlist, rules, devices=None, out=None):
+    """--stdout: the candidates of a rule search as the device spells them (ctx.spell_rules: after the format's cut),
+    one per line, decoded as found passwords are (:func:`rule_text`).  Verifies nothing.  Returns their number."""
+    out = sys.stdout if out is None else out
+    words = hybrid.read_wordlist(wordlist) if isinstance(wordlist, str) else [hybrid._bytes(w) for w in wordlist]
+    rules = load_rules(rules)
+    devs = _devices(devices)
+    ctx = _lib.Context(input_data, devices=devs[:1])
+    try:
+        words, rules, office = _rule_words(ctx, input_data, words, rules)
+        space = rulemod.space(len(words), len(rules))
+        if not space:
+            return 0
+        ctx.set_words(words)
+        table = rulemod.encode(rules)
+        raw = getattr(out, "buffer", None)
+        for start in range(0, space, _lib.MAX_SPELL):
+            lines = [rule_text(cand, office).encode("utf-8", "surrogatepass" if office else "surrogateescape")
+                     for cand in ctx.spell_rules(table, start, min(_lib.MAX_SPELL, space - start))]
+            data = b"\n".join(lines) + b"\n"
+            if raw is not None:                   # the candidates' own bytes, valid UTF-8 or not
+                out.flush()
+                raw.write(data)
+                raw.flush()
+            else:
+                out.write(data.decode("utf-8", "replace"))
+        return space
+    finally:
+        ctx.close()
+
+
 def init_listbased_brute_force(input_data, passwords, devices=None, owner=False):
     """An explicit candidate list, e.g. a server payload (brute_force.py:82-104): one library call over all
     devices; the lowest list index that verifies wins."""
@@ -545,6 +692,12 @@ def main(argv=None):
                         help="hybrid search: every word of this file (one per line) with the --mask around it, the "
                              "mask naming the word's place with ?w (i.e., ?w?d?d or ?d?d?d?d-?w; default ?w, the bare "
                              "words)")
+    parser.add_argument("--rules", action="append", default=None, metavar="FILE",
+                        help="rule search: every word of the --wordlist under every rule of this file (one rule per "
+                             "line, hashcat's functions : l u c C t TN E r d pN f { } q k K *NM $X ^X [ ] DN xNM ONM iNX "
+                             "oNX 'N zN ZN yN YN sXY @X .N ,N); given twice, the two files are multiplied")
+    parser.add_argument("--stdout", action="store_true",
+                        help="with --rules: print the candidates, one per line, and verify nothing")
     parser.add_argument("--owner", action="store_true",
                         help="search the PDF's owner password (the one that lifts print / copy / edit restrictions) "
                              "instead of its user password; document type 3 only")
@@ -552,6 +705,13 @@ def main(argv=None):
     parser.add_argument("--checkpoint", default=None, help="resumable cursor file (written after every round)")
     args = parser.parse_args(argv)
     customs = [getattr(args, "custom" + k) for k in "1234"]
+    if args.rules is not None:
+        if args.wordlist is None:
+            parser.error("--rules needs a --wordlist: rules are applied to its words")
+        if args.mask not in (None, "?w"):
+            parser.error("--rules applies to the bare words: give no --mask (or ?w) with it")
+        if len(args.rules) > 2:
+            parser.error("--rules may be given once or twice (two files are multiplied)")
     if args.wordlist is not None:
         if args.passwordrange is not None or args.charset is not None:
             raise ValueError("--wordlist replaces -pr/--passwordrange and --charset: give either a wordlist or a range")
@@ -572,7 +732,13 @@ def main(argv=None):
     if not stream:
         sys.exit(0)
     devices = [int(x) for x in args.devices.split(",")] if args.devices else None
-    if args.wordlist is not None:
+    if args.rules is not None and args.stdout:
+        n = print_rule_candidates(parse_verification_data(stream), args.wordlist, args.rules, devices=devices)
+        return 0, n
+    if args.rules is not None:
+        found, password = init(stream, None, None, devices=devices, checkpoint=args.checkpoint, owner=args.owner,
+                               wordlist=args.wordlist, rules=args.rules)
+    elif args.wordlist is not None:
         found, password = init(stream, None, None, devices=devices, checkpoint=args.checkpoint, mask=args.mask,
                                custom_charsets=customs, owner=args.owner, wordlist=args.wordlist)
     elif args.mask is not None:

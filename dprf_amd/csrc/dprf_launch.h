@@ -36,6 +36,12 @@ hipError_t launch_spell_mask(const dprf_mask_args &a, const uint32_t *tab, uint3
  * (wblob: packed bytes as u32 words, woff: a.nwords + 1 byte offsets) spelled before mask position a.word_at */
 hipError_t launch_spell_hybrid(const dprf_hybrid_args &a, const uint32_t *tab, const uint32_t *wblob,
                                const uint32_t *woff, uint32_t *slots, uint8_t *lens, hipStream_t s);
+/* rule windows (dprf_search_rules / dprf_spell_rules, dprf_kernels_rules.hip): a.count candidates, rule (a.r0 + g) %
+ * a.nrules of the table (fns: a.nfns function words, roff: a.nrules + 1 offsets) applied to word a.w0 + (a.r0 + g) /
+ * a.nrules, into slots / lens as launch_spell_hybrid */
+hipError_t launch_spell_rules(const dprf_rules_args &a, const uint32_t *fns, const uint32_t *roff,
+                              const uint32_t *wblob, const uint32_t *woff, uint32_t *slots, uint8_t *lens,
+                              hipStream_t s);
 hipError_t launch_pdf_r6(const dprf_enum &e, const dprf_pdf_params &p, const dprf_aes_tables *T,
                          dprf_results *R, uint32_t cap, uint32_t stop, hipStream_t s);
 #endif

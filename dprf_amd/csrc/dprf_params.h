@@ -83,6 +83,24 @@ struct dprf_hybrid_args {
     uint32_t bwords;                /* u32 words the device blob holds (the staging loads stay below it) */
 };
 
+/* Rule windows (dprf_search_rules / dprf_spell_rules, k_spell_rules): a rule of the call's rule table applied to a word
+ * of the context's table.  The rule table is uploaded once per call: one u32 per function (the function's character in
+ * bits 0-7, its parameters in bits 8-15 and 16-23) and nrules + 1 offsets.  Candidate g of a launch is rule
+ * (r0 + g) % nrules applied to word w0 + (r0 + g) / nrules; r0 + g stays below 2^32. */
+#define DPRF_RULE_FNS 32            /* = DPRF_MAX_RULE_FNS (include/dprf.h) */
+struct dprf_rules_args {
+    uint32_t count;                 /* candidates of the launch */
+    uint32_t trunc;                 /* bytes at or past it are never written (PDF R2-R4 32, R5 127, else ~0) */
+    uint32_t unit;                  /* bytes per unit: 1, or 2 for Office (UTF-16 code units) */
+    uint32_t w0;                    /* the chunk start's word index */
+    uint32_t r0;                    /* the chunk start's rule index, < nrules */
+    uint32_t nrules;                /* rules in the table (>= 1) */
+    uint32_t div_m, div_s;          /* u32 division by nrules (fastdiv_magic; unused for nrules = 1) */
+    uint32_t nfns;                  /* function words the device table holds */
+    uint32_t nwords;                /* words in the word table (>= 1) */
+    uint32_t bwords;                /* u32 words the device blob holds (the staging loads stay below it) */
+};
+
 /* Device results of one API call (accumulated over its launches). */
 struct dprf_results {
     uint32_t nhits;                 /* total hits (may exceed cap) */

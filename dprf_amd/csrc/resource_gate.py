@@ -37,6 +37,7 @@ SCRATCH_LIMIT = {
     "k_agile_kdf": 0,         # Office 2010 / 2013 Agile Encryption (dprf_kernels_agile.hip)
     "k_agile_check": 0,
     "k_spell_hybrid": 0,      # hybrid windows (dprf_search_hybrid, dprf_kernels_hybrid.hip)
+    "k_spell_rules": 0,       # rule windows (dprf_search_rules / dprf_spell_rules, dprf_kernels_rules.hip)
 }
 
 

@@ -324,6 +324,70 @@ int dprf_search_hybrid(dprf_ctx *ctx, const uint8_t *sym, const uint32_t *sym_of
                        int word_at, uint64_t start, uint64_t count, int stop_on_first, uint64_t *hits, int64_t cap,
                        int64_t *nhits, dprf_stats *stats);
 
+/* ---- rule mode: a word table times word-mangling rules ("password" -> "Password1", "p@ssw0rd", "drowssap") ----
+ * Additive to ABI 9 (DPRF_ABI_VERSION stays 9): a caller detects it by looking the symbol dprf_search_rules up.
+ *
+ * The language.  A rule is a sequence of 1..DPRF_MAX_RULE_FNS functions applied left to right to a word of the
+ * context's table (dprf_ctx_set_words).  A word is a sequence of units: for ODF and PDF a unit is a byte of the word as
+ * given, for Office (2007 and Agile) a UTF-16 code unit of the converted word.  LIMIT is 64 units for ODF and PDF and
+ * 32 units for Office: the 64-byte list slot.  The format's truncation applies to the result (PDF R2-R4 cut at 32
+ * bytes, R5 at 127).  Case functions touch ASCII letters only, in both unit widths.  A rule that splits a surrogate
+ * pair yields a candidate that no typed password spells; it is verified like any other candidate.
+ * Two rules hold for every function: a function whose result would be longer than LIMIT leaves the candidate
+ * unchanged, and so does a function whose result would be empty.  Together they keep every candidate at 1..LIMIT
+ * units with no NUL, as dprf_ctx_set_words guarantees for the words.
+ * N and M are positions, written 0-9A-Z in rule text, with the values 0..35; X and Y are one unit given as one byte,
+ * 0x01..0xFF (Office: 0x01..0x7F, which becomes that UTF-16 unit).  w is the candidate, n its length, w[a:b] a
+ * half-open slice, rev reversal; a function whose condition does not hold leaves the candidate unchanged:
+ *   :        w                                    l / u    A-Z -> a-z / a-z -> A-Z in every unit
+ *   c / C    l then unit 0 upper-cased / u then unit 0 lower-cased
+ *   t        toggle the case of every letter      TN       toggle unit N, if N < n
+ *   E        l, then upper-case unit 0 and every unit that follows a 0x20
+ *   r        rev w                                d        w + w
+ *   pN       w repeated N + 1 times               f        w + rev w
+ *   {  /  }  w[1:n] + w[0:1]  /  w[n-1:n] + w[0:n-1]
+ *   q        every unit twice                     k / K    swap units 0, 1 / units n-2, n-1, if n >= 2
+ *   *NM      swap units N and M, if N < n and M < n
+ *   $X / ^X  w + X / X + w                        [ / ]    w[1:n] / w[0:n-1]
+ *   DN       delete unit N, if N < n              xNM      w[N:N+M], if N + M <= n
+ *   ONM      w[0:N] + w[N+M:n], if N + M <= n     iNX      w[0:N] + X + w[N:n], if N <= n
+ *   oNX      unit N := X, if N < n                'N       w[0:N], if N < n
+ *   zN / ZN  w[0] x N + w  /  w + w[n-1] x N
+ *   yN / YN  w[0:N] + w  /  w + w[n-N:n], if N <= n
+ *   sXY      every unit equal to X becomes Y      @X       every unit equal to X is deleted
+ *   .N / ,N  unit N := unit N+1, if N + 1 < n  /  unit N := unit N-1, if 1 <= N < n
+ * These are hashcat's functions of the same names; its reject, memory and arithmetic functions are not included.
+ *
+ * The compiled form: one uint32 per function -- the function's own ASCII character in bits 0-7, the first parameter in
+ * bits 8-15, the second in bits 16-23 (N and M as their values, X and Y as the byte), everything else 0.  Rule k is
+ * fns[rule_off[k] .. rule_off[k+1]) (nrules + 1 offsets).  Candidate i of the keyspace N * R (N words, R rules) is
+ * rule i % R applied to word i / R: the word is the slowest digit, as in hybrid mode.
+ *
+ * dprf_search_rules verifies indices [start, start + count).  The rule table goes to each device once per call, per
+ * launch only the chunk start's word and rule index; the device applies the rules (k_spell_rules) and the list-mode
+ * kernels verify the slots.  hits[] relative to `start`, stop_on_first (the lowest verifying index), multi-device
+ * chunks, the cross-device stop, stats, owner mode, DPRF_FLAG_NEVER_MATCHES contexts and the per-device records are
+ * as dprf_search_hybrid's.
+ * dprf_spell_rules writes the candidates themselves: slot k of slots[count * 64] holds the bytes of candidate start + k
+ * after the format's cut (Office: UTF-16LE), zero-padded, and lens[k] their number -- exactly what a search would
+ * verify, spelled by the same kernel on the context's first device; no verification kernel runs.  count <= 2^20.
+ * Errors (a refused call leaves no per-device record, and the context still serves):
+ * DPRF_E_INVALID -- a null argument, no word table, nrules outside 1..DPRF_MAX_RULES, offsets not ascending, a rule of
+ * 0 or more than DPRF_MAX_RULE_FNS functions, more than DPRF_MAX_RULE_WORDS functions in all, start + count above
+ * N * R (computed without wrapping); for dprf_spell_rules also count above 2^20 or a never-matching context.
+ * DPRF_E_CHARSET (the message names the rule and the function) -- an unknown function byte, a position over 35, an X
+ * or Y of 0, for Office an X or Y of 0x80 or more, non-zero unused parameter bits.
+ * DPRF_E_PWLEN (the message names the word) -- the table's longest converted word exceeds 64 bytes, for every family
+ * including PDF R2-R4: a rule may move a word's tail to the front, so a clipped copy is not enough. */
+#define DPRF_MAX_RULES      (1 << 20)   /* rules per call                       */
+#define DPRF_MAX_RULE_FNS   32          /* functions per rule                   */
+#define DPRF_MAX_RULE_WORDS (1 << 22)   /* encoded functions per call, in all   */
+int dprf_search_rules(dprf_ctx *ctx, const uint32_t *fns, const uint32_t *rule_off, int64_t nrules, uint64_t start,
+                      uint64_t count, int stop_on_first, uint64_t *hits, int64_t cap, int64_t *nhits,
+                      dprf_stats *stats);
+int dprf_spell_rules(dprf_ctx *ctx, const uint32_t *fns, const uint32_t *rule_off, int64_t nrules, uint64_t start,
+                     uint64_t count, uint8_t *slots, uint8_t *lens);
+
 #ifdef __cplusplus
 }
 #endif
