@@ -45,6 +45,13 @@ DEVI uint32_t f_maj(uint32_t a, uint32_t b, uint32_t c) {
 }
 DEVI uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
 
+/* n / d for any u32 n by a multiply-high with the host's magic for d >= 2 (dprf_host.cpp fastdiv_magic); callers
+ * take d = 1 apart.  The one division of every digit step: range_candidate, R5, Agile, R6 and the spelling kernels. */
+DEVI uint32_t fastdiv(uint32_t n, uint32_t m, uint32_t s) {
+    uint32_t t = __umulhi(n, m);
+    return (t + ((n - t) >> 1)) >> s;
+}
+
 /* ------------------------------------------------------------------ SHA-1 (FIPS 180-4 6.1.2) */
 #define SHA1_IV0 0x67452301u
 #define SHA1_IV1 0xEFCDAB89u

@@ -23,11 +23,6 @@ struct cand {
     uint32_t len;                  /* bytes */
 };
 
-DEVI uint32_t fastdiv(uint32_t n, uint32_t m, uint32_t s) {
-    uint32_t t = __umulhi(n, m);
-    return (t + ((n - t) >> 1)) >> s;
-}
-
 /* Keyspace index start+g -> candidate, itertools.product order (brute_force.py:205): the digit at
  * position pwlen-1 varies fastest.  UTF16: emit UTF-16LE code units (Office; ASCII charset only). */
 template <bool UTF16>
@@ -148,9 +143,10 @@ DEVI void sha256_msg2(uint32_t m[32], uint32_t total, uint32_t out[8]) {
     if (two) sha256_compress(out, b1);
 }
 
-/* The file is compiled three times (Makefile): the Office kernels (DPRF_PART_OFFICE), the ODF kernels
+/* The file is compiled four times (Makefile): the Office kernels (DPRF_PART_OFFICE), the ODF kernels
  * (DPRF_PART_ODT) and the PDF R2-R5 kernels (DPRF_PART_PDF), each object with the LLVM machine-scheduler
- * strategy that measured fastest for it AND leaves its kernels without scratch (resource_gate.py). */
+ * strategy that measured fastest for it AND leaves its kernels without scratch (resource_gate.py), and the long-list
+ * prehash (DPRF_PART_LONG). */
 #if !defined(DPRF_PART_OFFICE) && !defined(DPRF_PART_ODT) && !defined(DPRF_PART_PDF) && !defined(DPRF_PART_LONG)
 #define DPRF_PART_OFFICE
 #define DPRF_PART_ODT
@@ -220,147 +216,6 @@ k_long_prehash(dprf_enum e, dprf_long_params lp, dprf_results *R, uint32_t cap, 
         if (k < 5 || !sha1) e.keys[(size_t)k * e.count + g] = h[k];
 }
 
-/* ================================================================== symbol windows (round 6) */
-/* Range mode over a charset whose symbols take several bytes (a --charset with non-ASCII characters: one symbol per
- * character, its UTF-8 -- for Office its UTF-16LE -- bytes): index g of the chunk -> the candidate's bytes in a list
- * slot, in itertools.product order over the symbols (brute_force.py:205), for the list-mode kernels to verify.  The
- * digits come as in range_candidate (the chunk start's digits from the host, g added with carries); the bytes are
- * assembled in the thread's column of an LDS tile and the block's slots leave it as consecutive 16-byte pieces.
- * Bytes at or past `trunc` (PDF R2-R4 hash 32, pdf...c:137) and past the slot are never written: the slot stays zero
- * there, as dprf_verify_list packs a truncated candidate. */
-__global__ void __launch_bounds__(256)
-k_spell_symbols(dprf_enum e, const uint32_t *symtab, uint32_t trunc, uint32_t *slots, uint8_t *lens) {
-    /* the block's 256 slots as [word][slot] with a row stride of 258 words: the byte stores of one word index and the
-     * 16-byte read-outs below both spread over the banks */
-    constexpr uint32_t ST = 258;
-    __shared__ uint32_t sym[256], syl[256];
-    __shared__ uint32_t tile[DPRF_SLOT_WORDS * ST];
-    const uint32_t tid = threadIdx.x;
-    sym[tid] = symtab[tid];
-    syl[tid] = symtab[256 + tid];
-#pragma unroll
-    for (int j = 0; j < DPRF_SLOT_WORDS; j++) tile[j * ST + tid] = 0u;
-    __syncthreads();
-    const uint32_t g = blockIdx.x * 256u + tid;
-    const uint32_t n = e.pwlen < DPRF_MAX_RANGE_LEN ? e.pwlen : DPRF_MAX_RANGE_LEN;
-    const uint32_t lim = trunc < 4u * DPRF_SLOT_WORDS ? trunc : 4u * DPRF_SLOT_WORDS;
-    if (g < e.count) {
-        /* the digits twice, last position first (as range_candidate): once for the length, once to store each
-         * symbol's bytes right to left from it -- no digit array */
-        uint32_t total = 0;
-        for (int pass = 0; pass < 2; pass++) {
-            uint32_t rem = g, carry = 0, pos = total;
-            for (int p = (int)n - 1; p >= 0; --p) {
-                const uint32_t q = e.cslen == 1 ? rem : fastdiv(rem, e.div_m, e.div_s);
-                uint32_t d = (uint32_t)e.sdig[p] + (rem - q * e.cslen) + carry;
-                carry = d >= e.cslen ? 1u : 0u;
-                d -= carry ? e.cslen : 0u;
-                rem = q;
-                const uint32_t k = syl[d];
-                if (pass == 0) {
-                    total += k;
-                } else {
-                    pos -= k;
-                    const uint32_t w = sym[d];
-                    uint8_t *tb = (uint8_t *)tile;
-                    for (uint32_t j = 0; j < k; j++)
-                        if (pos + j < lim) tb[4u * (((pos + j) >> 2) * ST + tid) + ((pos + j) & 3u)] = (uint8_t)(w >> (8u * j));
-                }
-            }
-        }
-        lens[g] = (uint8_t)(total < lim ? total : lim);
-    }
-    __syncthreads();
-    /* read-out: 16-byte piece u = 256 q + tid of the block's 16 KB of slots (slot u / 4, words 4 (u % 4) ..), so every
-     * store instruction of the block writes 4 KB of consecutive memory */
-    const uint32_t base = blockIdx.x * 256u;
-    uint4 *out = (uint4 *)(slots + (size_t)base * DPRF_SLOT_WORDS);
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint32_t u = 256u * q + tid, sl = u >> 2, w0 = 4u * (u & 3u);
-        if (base + sl < e.count)
-            out[u] = make_uint4(tile[w0 * ST + sl], tile[(w0 + 1) * ST + sl], tile[(w0 + 2) * ST + sl],
-                                tile[(w0 + 3) * ST + sl]);
-    }
-}
-/* ================================================================== mask windows */
-/* k_spell_symbols with a table and a radix per position (dprf_search_mask: "?u?l?l?d", a literal is a position of one
- * symbol): index g of the chunk -> the candidate's bytes in a list slot, in itertools.product order over the
- * positions' symbol lists, the last position fastest.  Per position the block reads a record {radix | start digit <<
- * 16, fastdiv magic, shift, base into the pool} and the pool entry base + digit (LE-packed symbol word, byte count);
- * records and pool are staged into LDS once per block -- 0.5 KB + up to 8 KB + 2 KB beside the 16.5 KB tile, 26.6 KB
- * in all, so six blocks (24 waves) fit a CU's 160 KB.  Every lane of a wave reads the same record (an LDS broadcast)
- * and the radix-1 test is wave-uniform; lanes differ only in the pool entry and in the symbol's byte count.  Tile
- * layout, trunc rule and read-out are k_spell_symbols'. */
-__global__ void __launch_bounds__(256)
-k_spell_mask(dprf_mask_args a, const uint32_t *tab, uint32_t *slots, uint8_t *lens) {
-    constexpr uint32_t ST = 258;
-    __shared__ uint32_t rec[DPRF_MASK_POOL_AT];
-    __shared__ uint32_t pw[DPRF_MASK_POOL];
-    __shared__ uint32_t plw[DPRF_MASK_POOL / 4];
-    __shared__ uint32_t tile[DPRF_SLOT_WORDS * ST];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t n = a.npos < DPRF_MAX_RANGE_LEN ? a.npos : DPRF_MAX_RANGE_LEN;
-    const uint32_t np = a.npool < DPRF_MASK_POOL ? a.npool : DPRF_MASK_POOL;
-    if (tid < DPRF_MASK_REC_WORDS * n) {
-        uint32_t v = tab[tid];
-        if ((tid & 3u) == 0u) {
-            /* position tid / 4: its start digit is byte (tid / 4) % 4 of a.sdig[tid / 16] (static indices only) */
-            uint32_t sw = 0;
-#pragma unroll
-            for (uint32_t j = 0; j < DPRF_MAX_RANGE_LEN / 4; j++) sw = (tid >> 4) == j ? a.sdig[j] : sw;
-            v |= ((sw >> (8u * ((tid >> 2) & 3u))) & 0xffu) << 16;
-        }
-        rec[tid] = v;
-    }
-    for (uint32_t k = tid; k < np; k += 256u) pw[k] = tab[DPRF_MASK_POOL_AT + k];
-    for (uint32_t k = tid; k < (np + 3u) >> 2; k += 256u) plw[k] = tab[DPRF_MASK_LENS_AT + k];
-#pragma unroll
-    for (int j = 0; j < DPRF_SLOT_WORDS; j++) tile[j * ST + tid] = 0u;
-    __syncthreads();
-    const uint32_t g = blockIdx.x * 256u + tid;
-    const uint32_t lim = a.trunc < 4u * DPRF_SLOT_WORDS ? a.trunc : 4u * DPRF_SLOT_WORDS;
-    if (g < a.count) {
-        const uint8_t *pl = (const uint8_t *)plw;
-        /* the digits twice, last position first: once for the length, once to store each symbol's bytes right to
-         * left from it (k_spell_symbols) */
-        uint32_t total = 0;
-        for (int pass = 0; pass < 2; pass++) {
-            uint32_t rem = g, carry = 0, pos = total;
-            for (int p = (int)n - 1; p >= 0; --p) {
-                const uint32_t r0 = rec[4 * p], radix = r0 & 0xffffu;
-                /* a literal takes no division: q = rem, digit 0, and a carry passes through it */
-                const uint32_t q = radix == 1u ? rem : fastdiv(rem, rec[4 * p + 1], rec[4 * p + 2]);
-                uint32_t d = (r0 >> 16) + (rem - q * radix) + carry;
-                carry = d >= radix ? 1u : 0u;
-                d -= carry ? radix : 0u;
-                rem = q;
-                const uint32_t en = (rec[4 * p + 3] + d) & (DPRF_MASK_POOL - 1u);
-                const uint32_t k = pl[en];
-                if (pass == 0) {
-                    total += k;
-                } else {
-                    pos -= k;
-                    const uint32_t w = pw[en];
-                    uint8_t *tb = (uint8_t *)tile;
-                    for (uint32_t j = 0; j < k; j++)
-                        if (pos + j < lim) tb[4u * (((pos + j) >> 2) * ST + tid) + ((pos + j) & 3u)] = (uint8_t)(w >> (8u * j));
-                }
-            }
-        }
-        lens[g] = (uint8_t)(total < lim ? total : lim);
-    }
-    __syncthreads();
-    const uint32_t base = blockIdx.x * 256u;
-    uint4 *out = (uint4 *)(slots + (size_t)base * DPRF_SLOT_WORDS);
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint32_t u = 256u * q + tid, sl = u >> 2, w0 = 4u * (u & 3u);
-        if (base + sl < a.count)
-            out[u] = make_uint4(tile[w0 * ST + sl], tile[(w0 + 1) * ST + sl], tile[(w0 + 2) * ST + sl],
-                                tile[(w0 + 3) * ST + sl]);
-    }
-}
 #endif /* DPRF_PART_LONG */
 
 #ifdef DPRF_PART_OFFICE
@@ -1546,16 +1401,6 @@ hipError_t launch_odt(const dprf_enum &e, const dprf_odt_params &p, const dprf_a
 hipError_t launch_long_prehash(const dprf_enum &e, const dprf_long_params &lp, dprf_results *R, uint32_t cap,
                                uint32_t stop, hipStream_t s) {
     hipLaunchKernelGGL(k_long_prehash, GRID(e.count, 256), dim3(256), 0, s, e, lp, R, cap, stop);
-    return hipGetLastError();
-}
-hipError_t launch_spell_symbols(const dprf_enum &e, const uint32_t *symtab, uint32_t trunc, uint32_t *slots,
-                                uint8_t *lens, hipStream_t s) {
-    hipLaunchKernelGGL(k_spell_symbols, GRID(e.count, 256), dim3(256), 0, s, e, symtab, trunc, slots, lens);
-    return hipGetLastError();
-}
-hipError_t launch_spell_mask(const dprf_mask_args &a, const uint32_t *tab, uint32_t *slots, uint8_t *lens,
-                             hipStream_t s) {
-    hipLaunchKernelGGL(k_spell_mask, GRID(a.count, 256), dim3(256), 0, s, a, tab, slots, lens);
     return hipGetLastError();
 }
 #endif

@@ -25,11 +25,6 @@ struct cand {
     uint32_t len;                  /* bytes */
 };
 
-DEVI uint32_t fastdiv(uint32_t n, uint32_t m, uint32_t s) {
-    uint32_t t = __umulhi(n, m);
-    return (t + ((n - t) >> 1)) >> s;
-}
-
 /* Keyspace index start+g -> candidate in itertools.product order, as UTF-16LE code units (ASCII charset only) */
 DEVI void range_candidate(const dprf_enum &e, const uint8_t *cs, uint32_t g, cand &c) {
 #pragma unroll

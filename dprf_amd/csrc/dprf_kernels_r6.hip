@@ -42,11 +42,6 @@
 #define R6_TE_USED (4 * R6_TABLES * R6_TE_COPIES)
 static_assert(R6_TE_USED <= R6_TE_ROW_BYTES && (R6_TE_COPIES & (R6_TE_COPIES - 1)) == 0, "table rows");
 
-DEVI uint32_t fastdiv6(uint32_t n, uint32_t m, uint32_t s) {
-    uint32_t t = __umulhi(n, m);
-    return (t + ((n - t) >> 1)) >> s;
-}
-
 /* static, so its LDS address is a link-time constant (0) and folds into the ds_read: the v_perm result is
  * the whole address */
 __shared__ __attribute__((aligned(16))) uint32_t r6_te[R6_TE_BYTES / 4];
@@ -253,7 +248,7 @@ DEVI uint32_t r6_begin(const dprf_enum &e, const dprf_pdf_params &p, const uint8
 #pragma unroll 1
         for (uint32_t k = 0; k < n; k++) {
             const uint32_t pp = n - 1u - k;
-            const uint32_t q = e.cslen == 1 ? rem : fastdiv6(rem, e.div_m, e.div_s);
+            const uint32_t q = e.cslen == 1 ? rem : fastdiv(rem, e.div_m, e.div_s);
             const uint32_t r = rem - q * e.cslen;
             uint32_t d = (uint32_t)sdig[pp] + r + carry;      /* LDS copy: a runtime index into the byval
                                                                  kernel argument would put it on the stack */

@@ -23,22 +23,23 @@ hipError_t launch_pdf_r24(const dprf_enum &e, const dprf_pdf_params &p, dprf_res
 /* long list (e.mode 2): the records' first-message hash into e.keys, or (DPRF_LONG_R5) the whole R5 check */
 hipError_t launch_long_prehash(const dprf_enum &e, const dprf_long_params &lp, dprf_results *R, uint32_t cap,
                                uint32_t stop, hipStream_t s);
+/* The four device spellers (dprf_kernels_spell.hip), each into slots[n][DPRF_SLOT_WORDS] / lens[n]; bytes at or past
+ * the trunc of the arguments stay zero. */
 /* symbol windows (dprf_search_symbols): e.count candidates from the digits in e.sdig (base e.cslen), symbol table
- * symtab = [256] LE-packed bytes + [256] byte counts, into slots[n][DPRF_SLOT_WORDS] / lens[n]; bytes at or past
- * trunc stay zero */
+ * symtab = [256] LE-packed bytes + [256] byte counts */
 hipError_t launch_spell_symbols(const dprf_enum &e, const uint32_t *symtab, uint32_t trunc, uint32_t *slots,
                                 uint8_t *lens, hipStream_t s);
 /* mask windows (dprf_search_mask): a.count candidates from the digits in a.sdig, position records and symbol pool in
- * tab (DPRF_MASK_TAB_WORDS words, dprf_params.h), into slots[n][DPRF_SLOT_WORDS] / lens[n] as launch_spell_symbols */
+ * tab (DPRF_MASK_TAB_WORDS words, dprf_params.h) */
 hipError_t launch_spell_mask(const dprf_mask_args &a, const uint32_t *tab, uint32_t *slots, uint8_t *lens,
                              hipStream_t s);
-/* hybrid windows (dprf_search_hybrid, dprf_kernels_hybrid.hip): as launch_spell_mask with a word of the table
+/* hybrid windows (dprf_search_hybrid): as launch_spell_mask with a word of the table
  * (wblob: packed bytes as u32 words, woff: a.nwords + 1 byte offsets) spelled before mask position a.word_at */
 hipError_t launch_spell_hybrid(const dprf_hybrid_args &a, const uint32_t *tab, const uint32_t *wblob,
                                const uint32_t *woff, uint32_t *slots, uint8_t *lens, hipStream_t s);
-/* rule windows (dprf_search_rules / dprf_spell_rules, dprf_kernels_rules.hip): a.count candidates, rule (a.r0 + g) %
+/* rule windows (dprf_search_rules / dprf_spell_rules): a.count candidates, rule (a.r0 + g) %
  * a.nrules of the table (fns: a.nfns function words, roff: a.nrules + 1 offsets) applied to word a.w0 + (a.r0 + g) /
- * a.nrules, into slots / lens as launch_spell_hybrid */
+ * a.nrules */
 hipError_t launch_spell_rules(const dprf_rules_args &a, const uint32_t *fns, const uint32_t *roff,
                               const uint32_t *wblob, const uint32_t *woff, uint32_t *slots, uint8_t *lens,
                               hipStream_t s);

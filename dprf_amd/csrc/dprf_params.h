@@ -1,5 +1,5 @@
 /* dprf_params.h -- kernel-argument structs shared by the host (dprf_host.cpp) and the gfx950 kernels
- * (dprf_kernels.hip).  Plain C layout; everything a kernel needs about one document is folded here
+ * (dprf_kernels*.hip).  Plain C layout; everything a kernel needs about one document is folded here
  * once per context, never per candidate.  Word conventions: "BE" = the 32-bit big-endian words that
  * SHA-1/SHA-2/AES operate on; "LE" = little-endian words (MD5, RC4 byte order, candidate bytes). */
 #ifndef DPRF_PARAMS_H
@@ -71,8 +71,9 @@ struct dprf_mask_args {
  * word_at, the word being one more digit at the most significant end of the mask's mixed radix.  The word table lives
  * on the device from dprf_ctx_set_words on: the converted bytes of all words packed back to back (each clipped to a
  * slot's 64 bytes), and nwords + 1 u32 byte offsets.  A block's 256 candidates use one contiguous run of at most
- * DPRF_HYB_RUN words, which the block stages into LDS: at most 16 KB of bytes, read as whole u32 words from the word
- * that holds the run's first byte (up to 3 bytes of lead-in, hence one word more). */
+ * DPRF_HYB_RUN words, which the block stages into LDS (dprf_kernels_spell.hip, "the word run"): at most 16 KB of bytes,
+ * read as whole u32 words from the word that holds the run's first byte (up to 3 bytes of lead-in, hence one word
+ * more).  Rule windows stage the same run. */
 #define DPRF_HYB_RUN 256
 #define DPRF_HYB_RUN_WORDS (DPRF_HYB_RUN * DPRF_SLOT_WORDS + 1)
 struct dprf_hybrid_args {

@@ -29,15 +29,15 @@ SCRATCH_LIMIT = {
     "k_pdf_r24": 0,
     "k_pdf_r6": 0,
     "k_long_prehash": 0,      # round 4: candidates longer than a list slot
-    "k_spell_symbols": 0,     # round 6: symbol windows (dprf_search_symbols)
-    "k_spell_mask": 0,        # mask windows (dprf_search_mask)
+    "k_spell_symbols": 0,     # the device spellers (dprf_kernels_spell.hip): symbol windows (dprf_search_symbols)
+    "k_spell_mask": 0,        # ... mask windows (dprf_search_mask)
     "k_pdf_r24_owner": 0,     # owner-password search (dprf_ctx_set_pdf_password)
     "k_pdf_r5_owner": 0,
     "k_pdf_r6_owner": 0,
     "k_agile_kdf": 0,         # Office 2010 / 2013 Agile Encryption (dprf_kernels_agile.hip)
     "k_agile_check": 0,
-    "k_spell_hybrid": 0,      # hybrid windows (dprf_search_hybrid, dprf_kernels_hybrid.hip)
-    "k_spell_rules": 0,       # rule windows (dprf_search_rules / dprf_spell_rules, dprf_kernels_rules.hip)
+    "k_spell_hybrid": 0,      # ... hybrid windows (dprf_search_hybrid)
+    "k_spell_rules": 0,       # ... rule windows (dprf_search_rules / dprf_spell_rules)
 }
 
 

@@ -1,4 +1,4 @@
-"""CPU restatement of k_spell_hybrid (dprf_amd/csrc/dprf_kernels_hybrid.hip) and of the host side that feeds it
+"""CPU restatement of k_spell_hybrid (dprf_amd/csrc/dprf_kernels_spell.hip) and of the host side that feeds it
 (dprf_host.cpp: dprf_ctx_set_words' packed table -- converted bytes clipped to a slot, u32 offsets --, and
 dprf_search_hybrid's mask table and per-launch arguments: the chunk start's mask digits and its word index) against an
 independent speller: divmod(i, M), the mask part by divmod over the positions, bytes concatenated in spelling order,
@@ -72,7 +72,7 @@ def host_args(radix, npool, trunc, word_at, nwords, bwords, first, count):
             "w0": v, "nwords": nwords, "bwords": bwords}
 
 
-# ------------------------------------------------------------------ device side (dprf_kernels_hybrid.hip)
+# ------------------------------------------------------------------ device side (dprf_kernels_spell.hip)
 def digit(rec, p, rem, carry):
     r0 = rec[4 * p]
     radix = r0 & 0xffff
@@ -265,7 +265,7 @@ M258 = [mm.table(2, 3), mm.table(129, 4)]
 
 def test_constants_are_the_kernel_s():
     assert RUN == 256 and "#define DPRF_HYB_RUN_WORDS (DPRF_HYB_RUN * DPRF_SLOT_WORDS + 1)" in PARAMS
-    kernel = open(os.path.join(CSRC, "dprf_kernels_hybrid.hip")).read()
+    kernel = open(os.path.join(CSRC, "dprf_kernels_spell.hip")).read()
     for text in ("__shared__ uint32_t soff[DPRF_HYB_RUN + 1];", "__shared__ uint32_t run[DPRF_HYB_RUN_WORDS];",
                  "w = a.w0 + rem + carry;", "constexpr uint32_t ST = 258;"):
         assert text in kernel, text

@@ -91,16 +91,18 @@ def test_header_library_and_binding_carry_the_new_symbols():
 def test_kernel_is_gated_and_built_into_its_own_object():
     csrc = os.path.join(REPO, "dprf_amd", "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read()
-    assert "$(OBJDIR)/dprf_kernels_hybrid.o: EXPECT := k_spell_hybrid" in mk
-    assert re.search(r"KOBJS\s+:=[^#]*dprf_kernels_hybrid\.o", mk, re.S) and "dprf_kernels_hybrid.hip $(HDRS)" in mk
-    assert re.search(r"BUILD_ID := .*dprf_kernels_hybrid\.hip", mk)
+    # the four spellers share one source and one object (dprf_kernels_spell.hip); each is an expected kernel of it
+    assert "$(OBJDIR)/dprf_kernels_spell.o: EXPECT := k_spell_symbols,k_spell_mask,k_spell_hybrid,k_spell_rules" in mk
+    assert re.search(r"KOBJS\s+:=[^#]*dprf_kernels_spell\.o", mk, re.S) and "dprf_kernels_spell.hip $(HDRS)" in mk
+    assert re.search(r"BUILD_ID := .*dprf_kernels_spell\.hip", mk)
+    assert "dprf_kernels_hybrid" not in mk and "dprf_kernels_rules" not in mk
     gate = {}
     exec(open(os.path.join(csrc, "resource_gate.py")).read().split("def parse")[0], gate)
     assert gate["SCRATCH_LIMIT"]["k_spell_hybrid"] == 0
     params = open(os.path.join(csrc, "dprf_params.h")).read()
     assert "#define DPRF_HYB_RUN 256" in params
     assert "#define DPRF_HYB_RUN_WORDS (DPRF_HYB_RUN * DPRF_SLOT_WORDS + 1)" in params
-    assert "k_spell_hybrid(dprf_hybrid_args a" in open(os.path.join(csrc, "dprf_kernels_hybrid.hip")).read()
+    assert "k_spell_hybrid(dprf_hybrid_args a" in open(os.path.join(csrc, "dprf_kernels_spell.hip")).read()
 
 
 STREAM = "x:$pdf$5*5*256*-1028*1*16*" + "0" * 32 + "*127*" + "0" * 254 + "*127*" + "0" * 254 + "*32*" + "0" * 64

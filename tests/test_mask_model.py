@@ -1,4 +1,4 @@
-"""CPU restatement of k_spell_mask (dprf_amd/csrc/dprf_kernels.hip) and of the host side that feeds it (dprf_host.cpp
+"""CPU restatement of k_spell_mask (csrc/dprf_kernels_spell.hip) and of the host side that feeds it (dprf_host.cpp
 dprf_search_mask: the merged symbol pool, the per-position records with their own fastdiv magic, the chunk start's
 mixed-radix digits packed into the kernel arguments) against an independent speller: itertools.product over the
 positions' symbol lists, "".join(...).encode(), truncated at the format's limit.
@@ -98,7 +98,7 @@ def host_args(radix, npool, trunc, first, count):
     return {"count": count, "npos": len(radix), "npool": npool, "trunc": trunc, "sdig": sdig}
 
 
-# ------------------------------------------------------------------ device side (dprf_kernels.hip)
+# ------------------------------------------------------------------ device side (dprf_kernels_spell.hip)
 def fastdiv(n, m, s):
     t = (n * m) >> 32
     return ((t + (((n - t) & M32) >> 1)) & M32) >> s

@@ -1,4 +1,4 @@
-"""CPU restatement of k_spell_symbols (dprf_amd/csrc/dprf_kernels.hip) and of the host side that feeds it
+"""CPU restatement of k_spell_symbols (dprf_amd/csrc/dprf_kernels_spell.hip) and of the host side that feeds it
 (dprf_host.cpp dprf_search_symbols: the symbol table, the chunk start's digits, the fastdiv magic) against an independent
 speller: divmod digits of the index, "".join(...).encode(), truncated at the format's limit.
 
@@ -82,7 +82,7 @@ def host_enum(nsym, pwlen, first, count):
     return {"count": count, "pwlen": pwlen, "cslen": nsym, "div_m": m, "div_s": s, "sdig": sdig}
 
 
-# ------------------------------------------------------------------ device side (dprf_kernels.hip)
+# ------------------------------------------------------------------ device side (dprf_kernels_spell.hip)
 def fastdiv(n, m, s):
     t = (n * m) >> 32
     return ((t + (((n - t) & M32) >> 1)) & M32) >> s
