@@ -190,7 +190,11 @@ def _check_window(start, count):
 
 class Context:
     """One document on one or more GPUs: the compiled form of the verifier argv brute_force.py builds per
-    candidate (brute_force.py:163-197).  ``devices``: a list of HIP ordinals (the library runs one worker
+    candidate (brute_force.py:163-197).  ``fields``: what parse_verification_data returns -- tag "office" (2007
+    Standard and 2010 / 2013 Agile Encryption; kernel families "office_std", "office_agile_sha1",
+    "office_agile_sha512"), "oldoffice" (Office 97-2003 RC4 types 0, 1, 3, 4; "office_rc4_md5", "office_rc4_sha1";
+    its ``format`` is FMT_OFFICE too), "odt" ("odf_aes256") or "pdf" ("pdf_r24", "pdf_r5", "pdf_r6" and their
+    "_owner" families).  ``devices``: a list of HIP ordinals (the library runs one worker
     thread and one stream per entry and splits every call over them); ``device``: one ordinal, or
     ALL_DEVICES for every gfx950 device.  ``pdf_password``: "user" (default) or "owner" -- which of a PDF's two
     passwords the searches verify (ABI 9, include/dprf.h dprf_ctx_set_pdf_password)."""

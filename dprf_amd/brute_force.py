@@ -60,6 +60,7 @@ ROUND_MAX_SECONDS = 12.0         # ... but never longer (R6's 2^25-ca
                                  # multi-GPU rounds ~36 s -- the checkpoint / Ctrl-C granularity; the guided split of
                                  # dprf_plan_chunk sizes the chunks of a shorter round down by itself)
 _HUGE = 1 << 62
+OFFICE_TAGS = ("office", "oldoffice")   # the streams of document type 1: their candidates are UTF-16 units
 
 
 def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, checkpoint=None, mask=None,
@@ -404,7 +405,7 @@ def _slot_fit(kernel, fields, words, positions):
     """Which words fit a 64-byte list slot with this mask around them, as dprf_search_hybrid counts: the converted
     word (Office: UTF-16LE) plus each position's longest symbol, after the format's truncation (PDF R2-R4 32 bytes
     -- every word fits --, R5 127).  Returns a list of bools."""
-    office = fields[0] == "office"
+    office = fields[0] in OFFICE_TAGS
     wide = (lambda b: len(b.decode("utf-8").encode("utf-16-le"))) if office else len
     room = 64 - sum(max(wide(ch.encode("utf-8")) for ch in p) for p in positions)
     if kernel.startswith("pdf_r24"):
@@ -510,7 +511,7 @@ def load_rules(rules):
 def _rule_words(ctx, input_data, words, rules):
     """The words and rules a rule search keeps: words no candidate can contain and words over 64 converted bytes are
     dropped (rules do not apply to them), and for Office so are rules with a unit over 0x7F.  Prints each count."""
-    office = input_data[0] == "office"
+    office = input_data[0] in OFFICE_TAGS
     status = ctx.words_status(words)
     bad = [k for k in range(len(words)) if status[k] != 0]
     if bad:
@@ -643,11 +644,27 @@ def get_verification_data(doc_type, filename):
 
 
 def parse_verification_data(stream):
-    """Field split + format tag (brute_force.py:245-264), verbatim semantics."""
+    """Field split + format tag (brute_force.py:245-264), verbatim semantics.
+
+    An Office 97-2003 stream (tag "oldoffice") comes in two spellings, both normalised to the five fields
+    ["oldoffice", type, salt, encryptedVerifier, encryptedVerifierHash]: the reference office2john's
+    ``$oldoffice$<type>*salt*ev*evh`` (four pieces, the type glued to the tag) and hashcat's / current John's
+    ``$oldoffice$*<type>*salt*ev*evh`` (five).  A ``:::...`` tail on the last field (John's GECOS fields) is cut off."""
     print("Preparing verification data...")
     data_array = re.split(r"(?:\*)", stream)
     m = re.search(r".*:\$(\w+)\$", data_array[0])
     data_format = m.groups()[0] if m else None
+    old = re.match(r"(?:.*:)?\$oldoffice\$([^*]*)$", data_array[0])   # with or without the "<file name>:" in front
+    if old:
+        data_format = "oldoffice"
+        if old.group(1):
+            data_array[1:1] = [old.group(1)]
+        data_array[-1] = data_array[-1].split(":::", 1)[0]
+        if len(data_array) == 5:
+            data_array[0] = data_format
+            return data_array
+        print("The input data is not supported.")
+        sys.exit(1)
     data_array[0] = data_format
     if data_format == "office" and len(data_array) == 8:
         return data_array
@@ -674,6 +691,7 @@ def main(argv=None):
             Actually supported formats:
                 Office Document Structure - EncryptionInfo Stream (Standard Encryption) (Office 2007)
                 Office Document Structure - EncryptionInfo Stream (Agile Encryption) (Office 2010 / 2013 and later)
+                Office Binary Document RC4 / RC4 CryptoAPI Encryption (Word and Excel 97 - 2003: .doc, .xls)
                 OpenDocument - v1.2 with AES-256 in CBC mode
                 Portable Document Format - PDF 1.3 - 1.7 (Standard Security Handlers v1-5 r2-6)
             """))

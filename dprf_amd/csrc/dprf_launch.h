@@ -13,6 +13,9 @@ hipError_t launch_office(const dprf_enum &e, const dprf_office_params &p, const 
 hipError_t launch_agile(const dprf_enum &e, const dprf_agile_params &p, const dprf_aes_tables *T,
                         dprf_results *R, uint32_t cap, uint32_t stop, hipStream_t s, uint32_t *keys,
                         hipEvent_t mid);
+/* Office 97-2003 RC4 (dprf_kernels_oldoffice.hip): one kernel per launch, no key hand-off; e.mode 0 or 1 */
+hipError_t launch_oldoffice(const dprf_enum &e, const dprf_oldoffice_params &p, dprf_results *R, uint32_t cap,
+                            uint32_t stop, hipStream_t s);
 hipError_t launch_odt(const dprf_enum &e, const dprf_odt_params &p, const dprf_aes_tables *T,
                       dprf_results *R, uint32_t cap, uint32_t stop, hipStream_t s, uint32_t *keys,
                          hipEvent_t mid);

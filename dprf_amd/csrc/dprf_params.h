@@ -145,6 +145,18 @@ struct dprf_agile_params {
     uint32_t key_words;             /* keyBits / 32: 4 or 8 */
 };
 
+/* Office 97-2003 RC4 and RC4 CryptoAPI (MS-OFFCRYPTO 2.3.6 / 2.3.5; include/dprf.h "Office 97-2003") */
+#define DPRF_OLDOFFICE_REP_WORDS 96
+struct dprf_oldoffice_params {
+    uint32_t sha1;                  /* 0: types 0 / 1 (MD5), 1: types 3 / 4 (SHA-1) */
+    uint32_t key_bytes;             /* SHA-1: 5 (type 3, zero-extended to a 16-byte RC4 key) or 16 (type 4) */
+    uint32_t salt[4];               /* SHA-1: BE words of the 16 salt bytes, the first message's prefix */
+    uint32_t ev[4];                 /* encryptedVerifier, LE words (RC4 byte order) */
+    uint32_t evh[5];                /* encryptedVerifierHash, LE words: 4 used by MD5, 5 by SHA-1 */
+    uint32_t rep[DPRF_OLDOFFICE_REP_WORDS]; /* MD5: the padded 336-byte message (h[0:5] || salt) x 16 as LE words of
+                                               six blocks, zeros where the five hash bytes of each copy go */
+};
+
 /* ODT: odt_password_verifier.c:51-126 */
 struct dprf_odt_params {
     uint32_t checksum[8];           /* BE */

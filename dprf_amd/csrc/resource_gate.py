@@ -38,6 +38,7 @@ SCRATCH_LIMIT = {
     "k_agile_check": 0,
     "k_spell_hybrid": 0,      # ... hybrid windows (dprf_search_hybrid)
     "k_spell_rules": 0,       # ... rule windows (dprf_search_rules / dprf_spell_rules)
+    "k_oldoffice": 0,         # Office 97-2003 RC4 / RC4 CryptoAPI (dprf_kernels_oldoffice.hip)
 }
 
 

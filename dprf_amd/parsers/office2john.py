@@ -9,6 +9,15 @@ Agile Encryption (Office 2010/2013) is printed in the reference's form too
 and libdprf.so verifies it on the device (kernel families "office_agile_sha1" / "office_agile_sha512",
 include/dprf.h "Agile"): keyBits 128 or 256, saltSize 16, spinCount up to 10,000,000.
 
+Password-protected binary documents of Office 97-2003 (no EncryptionInfo stream; the reference's process_file
+:1949-1982, find_rc4_passinfo_xls :1472-1537, find_rc4_passinfo_doc :1576-1629) are printed in the reference's form
+    ``<basename>:$oldoffice$<type>*<salt>*<encVerifier>*<encVerifierHash>``
+type 0 / 1: RC4 (MS-OFFCRYPTO 2.3.6) in an .xls / .doc, 16-byte verifier hash; type 3 / 4: RC4 CryptoAPI (2.3.5) with
+a 40-bit / 128-bit key, 20-byte verifier hash.  libdprf.so verifies them on the device (kernel families
+"office_rc4_md5" / "office_rc4_sha1", include/dprf.h "Office 97-2003").  The reference's ``:::summary::filename`` tail
+(John's GECOS fields, not verifier data) is left out.  XOR obfuscation and PowerPoint 97-2003 raise ValueError.  A
+.doc's header is read from the table stream its FIB names (fWhichTblStm); the reference always opens 1Table.
+
 The OLE compound file (MS-CFB) is read by a small reader of our own: header, DIFAT/FAT chains,
 directory, mini stream.
 """
@@ -86,9 +95,98 @@ class CompoundFile:
                 return self._chain_bytes(e["start"], e["size"], self.fat, self._sector)
         raise KeyError(name)
 
+    def has_stream(self, name):
+        return any(e["type"] == 2 and e["name"].lower() == name.lower() for e in self.entries[1:])
+
+
+def _cryptoapi(filename, s, off):
+    """RC4 CryptoAPI EncryptionHeader + EncryptionVerifier (MS-OFFCRYPTO 2.3.5.1) at s[off:], off just past the
+    version: (keySize, CSP name lower-cased, salt, encryptedVerifier, encryptedVerifierHash)."""
+    try:
+        header_size = struct.unpack_from("<I", s, off + 4)[0]         # after the 4 flag bytes
+        hdr = off + 8
+        key_size = struct.unpack_from("<I", s, hdr + 16)[0]           # flags, sizeExtra, algID, algIDHash, keySize
+        csp = s[hdr + 32:hdr + header_size].decode("utf-16-le", errors="replace").lower()
+        v = hdr + header_size
+        salt_size = struct.unpack_from("<I", s, v)[0]
+        if salt_size != 16:
+            raise ValueError("%s : salt size %d (expected 16)" % (filename, salt_size))
+        vh_size = struct.unpack_from("<I", s, v + 36)[0]
+        if vh_size != 20:
+            raise ValueError("%s : verifier hash size %d (expected 20)" % (filename, vh_size))
+        salt, ev, evh = s[v + 4:v + 20], s[v + 20:v + 36], s[v + 40:v + 60]
+    except struct.error:
+        raise ValueError("%s : truncated RC4 CryptoAPI header" % filename)
+    if len(evh) != 20:
+        raise ValueError("%s : truncated RC4 CryptoAPI verifier" % filename)
+    return key_size, csp, salt, ev, evh
+
+
+def _rc4_plain(filename, s, off):
+    """RC4 encryption header (MS-OFFCRYPTO 2.3.6.1) past its version: salt, encryptedVerifier, encryptedVerifierHash."""
+    if len(s) < off + 48:
+        raise ValueError("%s : truncated RC4 encryption header" % filename)
+    return s[off:off + 16], s[off + 16:off + 32], s[off + 32:off + 48]
+
+
+def _old_xls(filename, wb):
+    """FILEPASS (0x2F) of the Workbook stream's BIFF records -> (type, salt, ev, evh)."""
+    pos = 0
+    while pos + 4 <= len(wb):
+        rec, length = struct.unpack_from("<HH", wb, pos)
+        data = wb[pos + 4:pos + 4 + length]
+        pos += 4 + length
+        if rec != 0x2F:
+            continue
+        if data[0:2] == b"\x00\x00":
+            raise ValueError("%s : XOR obfuscation is not supported" % filename)
+        if data[0:6] == b"\x01\x00\x01\x00\x01\x00":
+            return (0,) + _rc4_plain(filename, data, 6)
+        if data[0:4] in (b"\x01\x00\x02\x00", b"\x01\x00\x03\x00"):
+            key_size, _, salt, ev, evh = _cryptoapi(filename, data, 6)
+            return (3 if key_size == 40 else 4, salt, ev, evh)
+        raise ValueError("%s : unknown FILEPASS encryption header %s" % (filename, data[0:6].hex()))
+    raise ValueError("%s : Document is not encrypted (no FILEPASS record)" % filename)
+
+
+def _old_doc(filename, cf):
+    """The FIB of WordDocument and the encryption header at the start of the table stream -> (type, salt, ev, evh)."""
+    fib = cf.open_stream("WordDocument")
+    if len(fib) < 12 or struct.unpack_from("<H", fib, 0)[0] != 0xA5EC:
+        raise ValueError("%s : WordDocument does not start with a FIB (wIdent 0xA5EC)" % filename)
+    flags = fib[11]                                   # bit 0 fEncrypted, bit 1 fWhichTblStm, bit 7 fObfuscated
+    if not flags & 0x01:
+        raise ValueError("%s : Document is not encrypted" % filename)
+    if flags & 0x80:
+        raise ValueError("%s : XOR obfuscation is not supported" % filename)
+    table = cf.open_stream("1Table" if flags & 0x02 else "0Table")
+    if len(table) < 4:
+        raise ValueError("%s : truncated table stream" % filename)
+    major, minor = struct.unpack_from("<HH", table, 0)
+    if major == 1 or minor == 1:
+        return (1,) + _rc4_plain(filename, table, 4)
+    if major >= 2 and minor == 2:
+        _, csp, salt, ev, evh = _cryptoapi(filename, table, 4)
+        return (4 if "strong" in csp else 3, salt, ev, evh)
+    raise ValueError("%s : unknown encryption header version %d.%d" % (filename, major, minor))
+
+
+def _old_office(filename, cf):
+    if cf.has_stream("WordDocument"):
+        typ, salt, ev, evh = _old_doc(filename, cf)
+    elif cf.has_stream("Workbook") or cf.has_stream("Book"):
+        typ, salt, ev, evh = _old_xls(filename, cf.open_stream("Workbook" if cf.has_stream("Workbook") else "Book"))
+    elif cf.has_stream("PowerPoint Document"):
+        raise ValueError("PowerPoint 97-2003 is not supported")
+    else:
+        raise KeyError("EncryptionInfo")
+    return "%s:$oldoffice$%d*%s*%s*%s" % (os.path.basename(filename), typ, salt.hex(), ev.hex(), evh.hex())
+
 
 def get_hash(filename):
     cf = CompoundFile(open(filename, "rb").read())
+    if not cf.has_stream("EncryptionInfo"):
+        return _old_office(filename, cf)
     s = cf.open_stream("EncryptionInfo")
     major, minor, flags = struct.unpack_from("<HHI", s, 0)
     if flags == 16:

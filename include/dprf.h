@@ -36,7 +36,8 @@ extern "C" {
 
 /* formats: the tag parse_verification_data extracts (brute_force.py:250) */
 #define DPRF_FMT_OFFICE 1   /* "$office$*2007*..."  ECMA-376 Standard Encryption; "$office$*2010*..." and
-                               "$office$*2013*..." Agile Encryption (below)                  */
+                               "$office$*2013*..." Agile Encryption (below); "$oldoffice$..."
+                               Office 97-2003 RC4 / RC4 CryptoAPI (below)                    */
 #define DPRF_FMT_ODT 2      /* "$odt$*1.2*..."      ODF 1.2 AES-256-CBC / PBKDF2-HMAC-SHA1     */
 #define DPRF_FMT_PDF 3      /* "$pdf$*V*R*..."      PDF standard security handler R2..R6       */
 
@@ -49,8 +50,8 @@ extern "C" {
 #define DPRF_E_NODEVICE (-4)     /* no usable gfx950 device / bad device ordinal                  */
 #define DPRF_E_PWLEN (-5)        /* candidate too long: over DPRF_MAX_PW bytes (list mode; no argv string can carry
                                     it to the reference), or a range length over DPRF_MAX_PW_RANGE; owner mode
-                                    (ABI 9): a PDF R5/R6 list candidate over the 64-byte slot; Office Agile: a
-                                    list candidate of more than 32 UTF-16 units                       */
+                                    (ABI 9): a PDF R5/R6 list candidate over the 64-byte slot; Office Agile and
+                                    Office 97-2003: a list candidate of more than 32 UTF-16 units     */
 #define DPRF_E_CHARSET (-6)      /* range charset invalid: empty, NUL, a repeated byte, or a byte >= 0x80
                                     for Office (its candidates are UTF-16LE of characters); symbols
                                     (dprf_search_symbols): empty, repeated, with a NUL byte or over 4
@@ -142,8 +143,8 @@ uint64_t dprf_plan_chunk(const char *kernel, double rate_per_ms, uint64_t remain
 
 /* ---- context: one document, one or more devices ----
  * fields/nfields: the array parse_verification_data() returns (brute_force.py:245-264), i.e. the
- * stream split on '*' with fields[0] replaced by the format tag ("office", "odt" or "pdf"); office
- * needs 8 fields, odt 7, pdf 12.  The per-format field meaning is exactly the reference's argv mapping
+ * stream split on '*' with fields[0] replaced by the format tag ("office", "oldoffice", "odt" or "pdf"); office
+ * needs 8 fields, oldoffice 5 (below), odt 7, pdf 12.  The per-format field meaning is exactly the reference's argv mapping
  * (brute_force.py:163-197).  device: HIP device ordinal, or DPRF_ALL_DEVICES for every gfx950 device. */
 int dprf_ctx_create(const char *const *fields, int nfields, int device, dprf_ctx **out);
 /* The same over an explicit device list (ABI 3).  An ordinal may repeat: {0,0} runs two streams and two
@@ -181,6 +182,42 @@ int dprf_ctx_last_call_devices(const dprf_ctx *ctx, dprf_device_stats *out, int 
  * that a list candidate of more than 32 UTF-16 units (the 64-byte slot) is DPRF_E_PWLEN, reported per candidate by
  * dprf_list_status: long Agile candidates are not supported yet. */
 #define DPRF_AGILE_MAX_SPIN 10000000
+
+/* ---- Office 97-2003 binary documents: RC4 (MS-OFFCRYPTO 2.3.6) and RC4 CryptoAPI (2.3.5) ----
+ * The stream office2john.py prints for a password-protected .doc / .xls: "$oldoffice$<type>*salt*ev*evh" (hashcat and
+ * current John write "$oldoffice$*<type>*..."; parse_verification_data takes both).  dprf_ctx_create takes
+ * fields[0] == "oldoffice" with nfields == 5: ["oldoffice", type, salt, encryptedVerifier, encryptedVerifierHash] --
+ * salt and encryptedVerifier 32 hex digits each, encryptedVerifierHash 32 hex digits for types 0 / 1 and 40 for types
+ * 3 / 4.  dprf_ctx_format returns DPRF_FMT_OFFICE (the reference's document type 1; candidates are UTF-16 units as for
+ * the other Office streams).  pw16 is the candidate in UTF-16LE, no terminator, no truncation; RC4 is one continuous
+ * keystream over both encrypted fields.
+ *   types 0, 1 (RC4, 40 bits of key material; the type only records the container, .xls / .doc):
+ *     h = MD5(pw16)
+ *     h = MD5((h[0:5] || salt) x 16)                              (336 bytes)
+ *     k = MD5(h[0:5] || 00 00 00 00)                              (block 0; all 16 bytes are the RC4 key)
+ *     d = RC4(k, encryptedVerifier || encryptedVerifierHash)      (32 bytes)
+ *     the candidate verifies when MD5(d[0:16]) == d[16:32]
+ *   types 3, 4 (RC4 CryptoAPI, 40-bit / 128-bit key):
+ *     h = SHA1(salt || pw16)
+ *     k = SHA1(h || 00 00 00 00)                                  (block 0)
+ *     key = k[0:5] || eleven 00 bytes (type 3: a 16-byte RC4 key, not a 5-byte one)   or   k[0:16] (type 4)
+ *     d = RC4(key, encryptedVerifier || encryptedVerifierHash)    (36 bytes)
+ *     the candidate verifies when SHA1(d[0:16]) == d[16:36]
+ * All 16 / 20 bytes are compared.  In types 0 / 1 only 40 bits of the first hash survive, so distinct passwords can
+ * verify: a search may return more than one hit.
+ * There is no reference verifier for this stream; the definition is pinned by the public example hashes of hashcat
+ * modes 9700 / 9800 (tests/golden/oldoffice_vectors.json: types 1 and 3).  No public type-4 vector is known: type 4
+ * differs from type 3 in the key cut alone and rests on the specification text.
+ * Accepted domain, anything else DPRF_E_DOMAIN with a message naming the field: type "0", "1", "3" or "4"; the three
+ * hex fields of exactly the lengths above.  Such a context sets no flag; dprf_ctx_set_pdf_password on it is
+ * DPRF_E_INVALID.  dprf_ctx_kernel returns "office_rc4_md5" (types 0, 1) or "office_rc4_sha1" (types 3, 4), families
+ * dprf_plan_chunk knows: a caller detects the support with dprf_plan_chunk("office_rc4_md5", 0, 1, 1, 1, 0) != 0
+ * (DPRF_ABI_VERSION is unchanged: no export or struct changed).  Range, symbol, mask, list, hybrid and rule modes work
+ * as for the 2007 stream (ASCII range charset, one valid UTF-8 character per symbol, empty or invalid UTF-8 list
+ * candidate DPRF_E_DOMAIN), except that a list candidate of more than 32 UTF-16 units (the 64-byte slot) is
+ * DPRF_E_PWLEN, reported per candidate by dprf_list_status: long Office 97-2003 candidates are not supported yet.
+ * Not done: PowerPoint 97-2003 (.ppt), XOR obfuscation, list candidates over 32 UTF-16 units, the 40-bit key-space
+ * attacks (hashcat modes 9710 / 9720 / 9810 / 9820), John's type 5, decrypting the document body. */
 
 /* ---- owner password (ABI 9): which of a PDF's two passwords the searches verify ----
  * A PDF carries a user password (opens the document) and an owner password (lifts the print / copy / edit
