@@ -649,7 +649,11 @@ def parse_verification_data(stream):
     An Office 97-2003 stream (tag "oldoffice") comes in two spellings, both normalised to the five fields
     ["oldoffice", type, salt, encryptedVerifier, encryptedVerifierHash]: the reference office2john's
     ``$oldoffice$<type>*salt*ev*evh`` (four pieces, the type glued to the tag) and hashcat's / current John's
-    ``$oldoffice$*<type>*salt*ev*evh`` (five).  A ``:::...`` tail on the last field (John's GECOS fields) is cut off."""
+    ``$oldoffice$*<type>*salt*ev*evh`` (five).  A ``:::...`` tail on the last field (John's GECOS fields) is cut off.
+
+    An ODF 1.0 / 1.1 stream (tag "odf", John's odf2john / hashcat 18600 spelling, what odt2hashes prints for a
+    Blowfish-CFB package) gives the 12 fields ["odf", "0", "0", iterations, "16", checksum, "8", iv, "16", salt, "0",
+    content]; a ``:::...`` tail is cut off here too."""
     print("Preparing verification data...")
     data_array = re.split(r"(?:\*)", stream)
     m = re.search(r".*:\$(\w+)\$", data_array[0])
@@ -666,6 +670,11 @@ def parse_verification_data(stream):
         print("The input data is not supported.")
         sys.exit(1)
     data_array[0] = data_format
+    if re.match(r"(?:.*:)?\$odf\$$", stream.split("*", 1)[0]):   # with or without the "<file name>:" in front
+        data_array[0] = "odf"
+        data_array[-1] = data_array[-1].split(":::", 1)[0]
+        if len(data_array) == 12:
+            return data_array
     if data_format == "office" and len(data_array) == 8:
         return data_array
     if data_format == "odt" and len(data_array) == 7:
@@ -693,6 +702,7 @@ def main(argv=None):
                 Office Document Structure - EncryptionInfo Stream (Agile Encryption) (Office 2010 / 2013 and later)
                 Office Binary Document RC4 / RC4 CryptoAPI Encryption (Word and Excel 97 - 2003: .doc, .xls)
                 OpenDocument - v1.2 with AES-256 in CBC mode
+                OpenDocument - v1.0 / 1.1 with Blowfish in CFB mode (OpenOffice.org, Apache OpenOffice, LibreOffice < 3.5)
                 Portable Document Format - PDF 1.3 - 1.7 (Standard Security Handlers v1-5 r2-6)
             """))
     parser.add_argument("document_type", help="type of the protected document")

@@ -16,6 +16,10 @@ hipError_t launch_agile(const dprf_enum &e, const dprf_agile_params &p, const dp
 /* Office 97-2003 RC4 (dprf_kernels_oldoffice.hip): one kernel per launch, no key hand-off; e.mode 0 or 1 */
 hipError_t launch_oldoffice(const dprf_enum &e, const dprf_oldoffice_params &p, dprf_results *R, uint32_t cap,
                             uint32_t stop, hipStream_t s);
+/* ODF 1.0 / 1.1 Blowfish (dprf_kernels_odf.hip): KDF on s_kdf, then the check on s_check (which may be s_kdf; if it is
+ * not, it waits for `mid`, which must then be given), four key words per candidate in `keys`; e.mode 0 or 1 */
+hipError_t launch_odf(const dprf_enum &e, const dprf_odf_params &p, dprf_results *R, uint32_t cap, uint32_t stop,
+                      hipStream_t s_kdf, hipStream_t s_check, uint32_t *keys, hipEvent_t mid);
 hipError_t launch_odt(const dprf_enum &e, const dprf_odt_params &p, const dprf_aes_tables *T,
                       dprf_results *R, uint32_t cap, uint32_t stop, hipStream_t s, uint32_t *keys,
                          hipEvent_t mid);

@@ -167,6 +167,17 @@ struct dprf_odt_params {
     const uint32_t *enc;            /* device: first hash_len bytes of ciphertext, BE words */
 };
 
+/* ODF 1.0 / 1.1: Blowfish-CFB, SHA-1 (include/dprf.h "ODF 1.0/1.1") */
+#define DPRF_ODF_CONTENT_WORDS 256  /* the first 1024 bytes of the encrypted entry */
+#define DPRF_ODF_X_WORDS (2 + DPRF_ODF_CONTENT_WORDS)
+struct dprf_odf_params {
+    uint32_t checksum[5];           /* SHA-1 of the first 1024 plaintext bytes, BE */
+    uint32_t salt[4];               /* BE */
+    uint32_t iterations;            /* PBKDF2 count, 1..DPRF_ODF_MAX_ITER */
+    const uint32_t *x;              /* device: iv || content[0:1024] as DPRF_ODF_X_WORDS BE words.  CFB block i is
+                                       pt_i = (x[2i + 2], x[2i + 3]) ^ E_key(x[2i], x[2i + 1]), i = 0..127 */
+};
+
 /* PDF: pdf_password_verifier.c:64-291 */
 #define DPRF_PDF_TAIL_WORDS 64
 #define DPRF_PDF_OSUF_WORDS 14

@@ -183,6 +183,9 @@ FLOOR = {
     # address is an immediate.  PRGA byte: j update, two addresses, xor into the output byte.
     "rc4_ksa": 256 * (2 * COST["add"] + COST["and"] + COST["shl"] + COST["or"]) + 64 * COST["add"],
     "rc4_prga_byte": 2 * COST["add"] + 2 * (COST["and"] + COST["shl"] + COST["or"]) + COST["shl"] + COST["xor"],
+    # Blowfish Feistel round with the boxes in LDS, [word][lane]: four byte extracts scaled to an address (extract,
+    # shift-or), F's add, xor, add, and the XOR of F and the subkey into the other half
+    "blowfish_round": 4 * (COST["bfe"] + COST["shl"]) + 2 * COST["add"] + COST["xor"] + COST["bitop3"],
 }
 # The instruction floor per primitive (module docstring).  AES with split T-tables in LDS: one v_perm address per
 # lookup, two v_bitop3 (XOR3) per output column of a round; the last round's 16 S-box bytes assembled by 3 v_perm per
@@ -206,6 +209,7 @@ INSTR = {
     "aes256_keyexp_dec_sched": 7 * (8 + 6 + 9) + 13 * 4 * (4 + 2),
     "rc4_ksa": 256 * (1 + 2) + 63,
     "rc4_prga_byte": 1 + 2 + 1 + 2 + 1,
+    "blowfish_round": 4 * 2 + 2 + 1,   # two per lookup address, v_add + v_xad, one v_bitop3 (the kernel has 13: DESIGN 4f)
 }
 # PDF R5 at its bench configuration (-pr 7: message words 0-1 carry the candidate, 2-15 are launch-uniform salt,
 # padding and length; the compare of IV7 + e after round 60 rejects all but 2^-32 of the candidates): the dataflow
@@ -218,9 +222,10 @@ SPEC = {   # SURVEY.md 8(d), VALU ops only (its AES / RC4 figures less their LDS
     "sha1c": 1001, "sha1c_office_loop": 1001, "sha1c_hmac20": 1001, "sha256c": 2296, "sha512c": 5840,
     "md5c": 532, "md5c_16": 532, "md5c_5": 532, "aes128_enc_block": 480, "aes128_dec_block": 480, "aes256_dec_block": 672,
     "aes128_keyexp": 0, "aes128_dec_sched": 0, "aes256_keyexp_dec_sched": 0, "rc4_ksa": 1280, "rc4_prga_byte": 11,
+    "blowfish_round": 11,
 }
 SPEC_LDS = {"aes128_enc_block": 160, "aes128_dec_block": 160, "aes256_dec_block": 224, "rc4_ksa": 1024,
-            "rc4_prga_byte": 5}   # LDS lane-operations per unit
+            "rc4_prga_byte": 5, "blowfish_round": 4}   # LDS lane-operations per unit
 LDS_LANE_OPS_PER_CYCLE = 32       # one conflict-free LDS access of 32 lanes per LDS-array cycle (a wave64 op: 2)
 # Formats whose spec count includes work the kernel by design does not execute (R5: rounds 61-63 after the early
 # reject, and the launch-uniform message words on the scalar unit): their spec_frac is an EFFECTIVE rate, not a
@@ -238,6 +243,10 @@ COUNTS = {
     # PBKDF2: ipad/opad midstates 2 + 2 blocks x (U1: 2 + 1023 x 2)
     "odt": {"sha256c": 18, "sha1c": 4, "sha1c_hmac20": 4094, "aes256_dec_block": 64, "aes256_keyexp_dec_sched": 1},
     "odt_e": {"sha256c": 1, "sha1c": 4, "sha1c_hmac20": 4094, "aes256_dec_block": 1, "aes256_keyexp_dec_sched": 1},
+    # ODF 1.0 / 1.1 at 1,024 iterations (family odf_bf_sha1; no bench.py workload): SHA1(pw) 1 + ipad/opad midstates 2
+    # + the 1 KiB checksum 17; PBKDF2 one block: U1 2 + 1023 x 2; Blowfish: (521 key-schedule + 128 CFB) encryptions
+    # of 16 rounds
+    "odf_legacy": {"sha1c": 20, "sha1c_hmac20": 2048, "blowfish_round": 649 * 16},
     # PDF R3/R4: initial MD5 2 blocks + 50 (16-byte message); 20 x (KSA + 16 PRGA bytes).
     # MD5(PAD || ID) is document-constant (the reference recomputes it per candidate, :167); not counted.
     "pdf_r34": {"md5c": 2, "md5c_16": 50, "rc4_ksa": 20, "rc4_prga_byte": 320},
@@ -254,12 +263,15 @@ MAIN = {
     "office": {"sha1c_office_loop": 50000, "sha1c": 4},
     "odt": {"sha256c": 1, "sha1c": 4, "sha1c_hmac20": 4094},
     "odt_e": {"sha256c": 1, "sha1c": 4, "sha1c_hmac20": 4094},
+    "odf_legacy": {"sha1c": 3, "sha1c_hmac20": 2048},
 }
 # which resource bounds each format when no current rocprof profile says otherwise.  The RC4 formats saturate
 # neither pipe (R3/R4 VALUBusy 0.73, LdsUtil 0.52: each wave's KSA is a chain of one dependent LDS round trip per
 # two steps); VALU is the busier of the two, so that is what their fraction is quoted against.
 BOUND = {"office": "valu", "odt": "valu", "odt_e": "valu", "pdf_r34": "valu", "pdf_r3_40": "valu", "pdf_r2": "valu",
-         "pdf_r5": "valu", "pdf_r6": "valu"}
+         "pdf_r5": "valu", "pdf_r6": "valu",
+         # the check kernel, most of this family's time, is a chain of LDS round trips at one wave per CU
+         "odf_legacy": "lds_latency"}
 
 
 # LDS-array cycles per candidate of the RC4 formats, from MI355X_MICROARCH.md's LDS table: every byte / u16 / dword

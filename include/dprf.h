@@ -38,7 +38,8 @@ extern "C" {
 #define DPRF_FMT_OFFICE 1   /* "$office$*2007*..."  ECMA-376 Standard Encryption; "$office$*2010*..." and
                                "$office$*2013*..." Agile Encryption (below); "$oldoffice$..."
                                Office 97-2003 RC4 / RC4 CryptoAPI (below)                    */
-#define DPRF_FMT_ODT 2      /* "$odt$*1.2*..."      ODF 1.2 AES-256-CBC / PBKDF2-HMAC-SHA1     */
+#define DPRF_FMT_ODT 2      /* "$odt$*1.2*..."      ODF 1.2 AES-256-CBC / PBKDF2-HMAC-SHA1;
+                               "$odf$*0*0*..."      ODF 1.0 / 1.1 Blowfish-CFB, SHA-1 (below)  */
 #define DPRF_FMT_PDF 3      /* "$pdf$*V*R*..."      PDF standard security handler R2..R6       */
 
 /* error codes */
@@ -51,7 +52,8 @@ extern "C" {
 #define DPRF_E_PWLEN (-5)        /* candidate too long: over DPRF_MAX_PW bytes (list mode; no argv string can carry
                                     it to the reference), or a range length over DPRF_MAX_PW_RANGE; owner mode
                                     (ABI 9): a PDF R5/R6 list candidate over the 64-byte slot; Office Agile and
-                                    Office 97-2003: a list candidate of more than 32 UTF-16 units     */
+                                    Office 97-2003: a list candidate of more than 32 UTF-16 units; ODF
+                                    1.0 / 1.1: a list candidate over the 64-byte slot                 */
 #define DPRF_E_CHARSET (-6)      /* range charset invalid: empty, NUL, a repeated byte, or a byte >= 0x80
                                     for Office (its candidates are UTF-16LE of characters); symbols
                                     (dprf_search_symbols): empty, repeated, with a NUL byte or over 4
@@ -143,8 +145,8 @@ uint64_t dprf_plan_chunk(const char *kernel, double rate_per_ms, uint64_t remain
 
 /* ---- context: one document, one or more devices ----
  * fields/nfields: the array parse_verification_data() returns (brute_force.py:245-264), i.e. the
- * stream split on '*' with fields[0] replaced by the format tag ("office", "oldoffice", "odt" or "pdf"); office
- * needs 8 fields, oldoffice 5 (below), odt 7, pdf 12.  The per-format field meaning is exactly the reference's argv mapping
+ * stream split on '*' with fields[0] replaced by the format tag ("office", "oldoffice", "odt", "odf" or "pdf"); office
+ * needs 8 fields, oldoffice 5 (below), odt 7, odf 12 (below), pdf 12.  The per-format field meaning is exactly the reference's argv mapping
  * (brute_force.py:163-197).  device: HIP device ordinal, or DPRF_ALL_DEVICES for every gfx950 device. */
 int dprf_ctx_create(const char *const *fields, int nfields, int device, dprf_ctx **out);
 /* The same over an explicit device list (ABI 3).  An ordinal may repeat: {0,0} runs two streams and two
@@ -218,6 +220,40 @@ int dprf_ctx_last_call_devices(const dprf_ctx *ctx, dprf_device_stats *out, int 
  * DPRF_E_PWLEN, reported per candidate by dprf_list_status: long Office 97-2003 candidates are not supported yet.
  * Not done: PowerPoint 97-2003 (.ppt), XOR obfuscation, list candidates over 32 UTF-16 units, the 40-bit key-space
  * attacks (hashcat modes 9710 / 9720 / 9810 / 9820), John's type 5, decrypting the document body. */
+
+/* ---- ODF 1.0 / 1.1: Blowfish in CFB mode, SHA-1 (OpenOffice.org, StarOffice, Apache OpenOffice, LibreOffice < 3.5
+ * and its "ODF 1.0/1.1" setting) ----
+ * The stream odt2hashes.py prints for a package whose manifest names the algorithm "Blowfish CFB"; it is the one John's
+ * odf2john and hashcat mode 18600 use:
+ *   $odf$*0*0*<iterations>*16*<checksum, 40 hex>*8*<iv, 16 hex>*16*<salt, 32 hex>*0*<content, 2048 hex>
+ * cipher 0 = Blowfish, checksum type 0 = SHA-1, key size 16, IV length 8, salt length 16, the "inplace" flag 0, and the
+ * first 1024 bytes of the encrypted entry.  dprf_ctx_create takes fields[0] == "odf" with nfields == 12: ["odf", "0",
+ * "0", iterations, "16", checksum, "8", iv, "16", salt, "0", content] (parse_verification_data cuts a ":::" tail off
+ * the last field).  dprf_ctx_format returns DPRF_FMT_ODT (the reference's document type 2; candidates are raw bytes,
+ * as for the ODF 1.2 stream).
+ *   sk  = SHA1(pw)                                   pw: the candidate's bytes as given (UTF-8)
+ *   key = PBKDF2-HMAC-SHA1(P = sk (20 bytes), S = salt, c = iterations, dkLen = 16)        (one output block)
+ *   pt  = Blowfish-CFB64-decrypt(key (16 bytes), iv, content[0:1024]):
+ *         pt_i = ct_i XOR E_key(ct_(i-1)), ct_(-1) = iv, 128 blocks of 8 bytes, big-endian halves
+ *   the candidate verifies when SHA1(pt) == checksum, all 20 bytes
+ * CFB decryption uses Blowfish's encrypt direction only, and every E_key input is a constant of the document.
+ * There is no reference verifier for this stream and no public test vector of it is at hand: the definition rests on
+ * tests/odf_legacy_model.py -- hashlib's SHA-1 and PBKDF2, and a Blowfish of its own whose initial words (the digits
+ * of pi, computed there), key schedule and CFB output are checked against libcrypto (BF_set_key, BF_cfb64_encrypt) and
+ * Schneier's zero-key vector.
+ * Accepted domain, anything else DPRF_E_DOMAIN with a message naming the field: cipher "0" and checksum type "0"; key
+ * size "16", IV length "8", salt length "16", inplace "0"; the hex fields of exactly the lengths above; iterations a
+ * decimal in 1..DPRF_ODF_MAX_ITER (a kernel argument; real files say 1024).  The AES spelling of the same stream,
+ * "$odf$*1*1*...", is refused with a message saying that ODF 1.2 documents go in as "$odt$".  Such a context sets no
+ * flag; dprf_ctx_set_pdf_password on it is DPRF_E_INVALID.  dprf_ctx_kernel returns "odf_bf_sha1", a family
+ * dprf_plan_chunk knows: a caller detects the support with dprf_plan_chunk("odf_bf_sha1", 0, 1, 1, 1, 0) != 0
+ * (DPRF_ABI_VERSION is unchanged: no export or struct changed).  Range, symbol, mask, list, hybrid and rule modes work
+ * as for the "$odt$" stream (raw bytes, rule unit = byte), except that a list candidate over the 64-byte slot is
+ * DPRF_E_PWLEN, reported per candidate by dprf_list_status: long ODF 1.0/1.1 candidates are not supported yet.
+ * Not done: content shorter than 1024 bytes (old OpenOffice builds wrote a defective SHA-1 for some lengths),
+ * StarOffice / OpenOffice.org 1.x packages (.sxw, .sxc), the "$odf$*1*1*" spelling, candidates over 64 bytes,
+ * decrypting the document. */
+#define DPRF_ODF_MAX_ITER 10000000
 
 /* ---- owner password (ABI 9): which of a PDF's two passwords the searches verify ----
  * A PDF carries a user password (opens the document) and an owner password (lifts the print / copy / edit
