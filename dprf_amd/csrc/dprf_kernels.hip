@@ -15,106 +15,13 @@
 #include "dprf_params.h"
 #include "dprf_launch.h"
 #include "dprf_hits.h"
+#include "dprf_cand.h"
 #include "rc4_dev.h"
 
-/* ------------------------------------------------------------------ candidate source */
-struct cand {
-    uint32_t w[DPRF_SLOT_WORDS];   /* LE-packed bytes (UTF-16LE code units for Office) */
-    uint32_t len;                  /* bytes */
-};
-
-/* Keyspace index start+g -> candidate, itertools.product order (brute_force.py:205): the digit at
- * position pwlen-1 varies fastest.  UTF16: emit UTF-16LE code units (Office; ASCII charset only). */
-template <bool UTF16>
-DEVI void range_candidate(const dprf_enum &e, const uint8_t *cs, uint32_t g, cand &c) {
-#pragma unroll
-    for (int j = 0; j < DPRF_SLOT_WORDS; j++) c.w[j] = 0;
-    uint32_t rem = g, carry = 0;
-#pragma unroll
-    for (int p = DPRF_MAX_RANGE_LEN - 1; p >= 0; --p) {
-        if ((uint32_t)p < e.pwlen) {
-            uint32_t q = e.cslen == 1 ? rem : fastdiv(rem, e.div_m, e.div_s);
-            uint32_t r = rem - q * e.cslen;
-            uint32_t d = (uint32_t)e.sdig[p] + r + carry;
-            carry = d >= e.cslen ? 1u : 0u;
-            d -= carry ? e.cslen : 0u;
-            rem = q;
-            uint32_t ch = cs[d];
-            if (UTF16) c.w[p >> 1] |= ch << (16 * (p & 1));
-            else c.w[p >> 2] |= ch << (8 * (p & 3));
-        }
-    }
-    c.len = UTF16 ? 2 * e.pwlen : e.pwlen;
-}
-
-DEVI void list_candidate(const dprf_enum &e, uint32_t g, cand &c) {
-    const uint64_t slot = e.start + g;
-    const uint4 *s = (const uint4 *)(e.slots + slot * DPRF_SLOT_WORDS);
-#pragma unroll
-    for (int q = 0; q < DPRF_SLOT_WORDS / 4; q++) {
-        uint4 v = s[q];
-        c.w[4 * q + 0] = v.x; c.w[4 * q + 1] = v.y; c.w[4 * q + 2] = v.z; c.w[4 * q + 3] = v.w;
-    }
-    c.len = e.lens[slot];
-}
-
-template <int MODE, bool UTF16>
-DEVI void get_candidate(const dprf_enum &e, const uint8_t *cs, uint32_t g, cand &c) {
-    if (MODE == 0) range_candidate<UTF16>(e, cs, g, c);
-    else list_candidate(e, g, c);
-}
-
-/* ------------------------------------------------------------------ block prologue / epilogue */
-/* Stage the charset (and optionally the AES tables) into LDS and decide once per block whether it runs.
- * With stop_on_first a block is skipped only when its LOWEST candidate index lies above the lowest hit
- * known so far (R->first, and across devices the call's, dprf_hits.h): every index below the final `first` is then verified whatever order the
- * workgroups are dispatched in, so the reported hit is the lowest of the call unconditionally (a boolean
- * stop flag would let a late-dispatched lower block skip itself).  `per` = candidates per thread.
- * COUNT: this kernel's skipped blocks are counted in R->skipped (the verifying kernel of a format; the
- * KDF kernels of Office/ODF skip exactly the blocks their check kernel skips and do not count). */
-template <bool AES, bool COUNT = true, bool STAGE_CS = true>
-DEVI bool block_prologue(const dprf_enum &e, const dprf_aes_tables *T, dprf_results *R, uint32_t stop_on_first,
-                         uint8_t *cs, aes_lds *L, uint32_t *flag, uint32_t per = 1) {
-    const uint32_t tid = threadIdx.x;
-    if (STAGE_CS)
-        for (uint32_t k = tid; k < 64; k += blockDim.x) ((uint32_t *)cs)[k] = ((const uint32_t *)e.charset)[k];
-    if (AES) {
-        for (uint32_t k = tid; k < 256; k += blockDim.x) { L->te[k] = T->te0[k]; L->td[k] = T->td0[k]; }
-        for (uint32_t k = tid; k < 64; k += blockDim.x) {
-            L->sb[k] = ((const uint32_t *)T->sbox)[k];
-            L->isb[k] = ((const uint32_t *)T->inv_sbox)[k];
-        }
-    }
-    if (tid == 0) {
-        uint32_t skip = 0u;
-        if (stop_on_first) {
-            const uint32_t off = blockIdx.x * blockDim.x * per;
-            skip = e.start + off > lowest_known(e, R) ? 1u : 0u;
-            if (skip && COUNT) {
-                const uint32_t n = e.count - off < blockDim.x * per ? e.count - off : blockDim.x * per;
-                atomicAdd(&R->skipped, (unsigned long long)n);
-            }
-        }
-        *flag = skip;
-    }
-    __syncthreads();
-    return *flag == 0;
-}
-
-
-/* BE message words of `len` candidate bytes (LE-packed) placed after `pre` bytes already in m[],
- * pre a multiple of 4 and <= 16, with the 0x80 terminator.  Static indices only.  A candidate that fills its whole
- * 64-byte slot (Office: 32 UTF-16 units; ODF: 64 bytes) has its terminator in the word after the slot (round 5: until
- * then it was dropped, and such a password was never found). */
-template <int PREW>
-DEVI void be_append(uint32_t m[32], const cand &c) {
-#pragma unroll
-    for (int j = 0; j < DPRF_SLOT_WORDS; j++)
-        m[PREW + j] = bswap32((c.w[j] & le_keep_mask(j, c.len)) | le_pad80(j, c.len));
-#pragma unroll
-    for (int j = PREW + DPRF_SLOT_WORDS; j < 32; j++) m[j] = 0;
-    m[PREW + DPRF_SLOT_WORDS] = c.len == 4u * DPRF_SLOT_WORDS ? 0x80000000u : 0u;
-}
+/* The candidate source, the block prologue and be_append are dprf_cand.h's.  The kernels of this file read a list
+ * candidate's length byte unclamped (get_candidate<MODE, UTF16, LIST_CLAMP>): the four objects built from it are the
+ * measured ones and keep their machine code, and the host never packs more than a slot. */
+#define LIST_CLAMP false
 
 /* SHA-1 / SHA-256 of a <= 119-byte message held in m[32] (BE, already terminated with 0x80):
  * one or two blocks, chosen per lane. */
@@ -240,7 +147,7 @@ k_office_kdf(dprf_enum e, dprf_office_params p, dprf_results *R, uint32_t stop_o
         for (int k = 0; k < 5; k++) h[k] = keys[(size_t)k * e.count + g];
     } else {
         cand c;
-        get_candidate<MODE, true>(e, cs, g, c);
+        get_candidate<MODE, true, LIST_CLAMP>(e, cs, g, c);
         /* H0 = SHA1(salt[0:16] || UTF16LE(pw)) (msoffcrypto...c:94-101) */
         uint32_t m[32];
         m[0] = p.salt[0]; m[1] = p.salt[1]; m[2] = p.salt[2]; m[3] = p.salt[3];
@@ -346,7 +253,7 @@ k_odt_kdf(dprf_enum e, dprf_odt_params p, dprf_results *R, uint32_t stop_on_firs
         for (int k = 0; k < 8; k++) sk[k] = keys[(size_t)k * e.count + g];
     } else {
         cand c;
-        get_candidate<MODE, false>(e, cs, g, c);
+        get_candidate<MODE, false, LIST_CLAMP>(e, cs, g, c);
         uint32_t m[32];
         be_append<0>(m, c);
         sha256_msg2(m, c.len, sk);
@@ -703,7 +610,7 @@ k_pdf_r5(dprf_enum e, dprf_pdf_params p, dprf_results *R, uint32_t cap, uint32_t
         const bool valid = g0 < e.count;
         const uint32_t g = valid ? g0 : e.count - 1;
         cand c;
-        get_candidate<MODE, false>(e, cs, g, c);
+        get_candidate<MODE, false, LIST_CLAMP>(e, cs, g, c);
         if (MODE == 0) {
             /* range_candidate leaves the bytes past pwlen zero */
             uint32_t b[16];
@@ -773,7 +680,7 @@ template <int MODE, int R, int NK>
 DEVI void r24_key(const dprf_enum &e, const dprf_pdf_params &p, const uint8_t *cs, const uint32_t *padw,
                   const uint32_t padtail[8], uint32_t g, uint32_t h[4]) {
     cand c;
-    get_candidate<MODE, false>(e, cs, g, c);
+    get_candidate<MODE, false, LIST_CLAMP>(e, cs, g, c);
     const uint32_t len = c.len > 32u ? 32u : c.len;
     uint32_t pw[8];
     if (MODE == 0) {
@@ -1005,7 +912,7 @@ template <int MODE>
 DEVI void r24_padded_pw(const dprf_enum &e, const uint8_t *cs, const uint32_t *padw, const uint32_t padtail[8],
                         uint32_t g, uint32_t pw[8]) {
     cand c;
-    get_candidate<MODE, false>(e, cs, g, c);
+    get_candidate<MODE, false, LIST_CLAMP>(e, cs, g, c);
     const uint32_t len = c.len > 32u ? 32u : c.len;
     if (MODE == 0) {
 #pragma unroll
@@ -1314,7 +1221,7 @@ k_pdf_r5_owner(dprf_enum e, dprf_pdf_params p, dprf_results *R, uint32_t cap, ui
         const bool valid = g0 < e.count;
         const uint32_t g = valid ? g0 : e.count - 1;
         cand c;
-        get_candidate<MODE, false>(e, cs, g, c);
+        get_candidate<MODE, false, LIST_CLAMP>(e, cs, g, c);
         uint32_t hh[8];
         sha256_iv(hh);
         if (MODE == 0) {
@@ -1369,7 +1276,6 @@ k_pdf_r5_owner(dprf_enum e, dprf_pdf_params p, dprf_results *R, uint32_t cap, ui
 #endif /* DPRF_PART_PDF */
 
 /* ------------------------------------------------------------------ launchers */
-#define GRID(n, b) dim3(((n) + (b) - 1) / (b))
 
 #ifdef DPRF_PART_OFFICE
 hipError_t launch_office(const dprf_enum &e, const dprf_office_params &p, const dprf_aes_tables *T,

@@ -11,104 +11,15 @@
  * definition is pinned by tests/agile_model.py and the public vectors in tests/golden/agile_vectors.json.
  *
  * A translation unit of its own: the kernels measured by bench.py (dprf_kernels.hip, dprf_kernels_r6.hip) keep their
- * objects untouched.  The candidate source and the block prologue are restated from dprf_kernels.hip.
+ * objects untouched.  The candidate source, the block prologue and be_append are dprf_cand.h's.
  */
 #include "dev_crypto.h"
 #include "dprf_params.h"
 #include "dprf_launch.h"
 #include "dprf_hits.h"
+#include "dprf_cand.h"
 
-/* ------------------------------------------------------------------ candidate source (as dprf_kernels.hip) */
 namespace {
-struct cand {
-    uint32_t w[DPRF_SLOT_WORDS];   /* LE-packed UTF-16LE code units */
-    uint32_t len;                  /* bytes */
-};
-
-/* Keyspace index start+g -> candidate in itertools.product order, as UTF-16LE code units (ASCII charset only) */
-DEVI void range_candidate(const dprf_enum &e, const uint8_t *cs, uint32_t g, cand &c) {
-#pragma unroll
-    for (int j = 0; j < DPRF_SLOT_WORDS; j++) c.w[j] = 0;
-    uint32_t rem = g, carry = 0;
-#pragma unroll
-    for (int p = DPRF_MAX_RANGE_LEN - 1; p >= 0; --p) {
-        if ((uint32_t)p < e.pwlen) {
-            uint32_t q = e.cslen == 1 ? rem : fastdiv(rem, e.div_m, e.div_s);
-            uint32_t r = rem - q * e.cslen;
-            uint32_t d = (uint32_t)e.sdig[p] + r + carry;
-            carry = d >= e.cslen ? 1u : 0u;
-            d -= carry ? e.cslen : 0u;
-            rem = q;
-            uint32_t ch = cs[d];
-            c.w[p >> 1] |= ch << (16 * (p & 1));
-        }
-    }
-    c.len = 2 * e.pwlen;
-}
-
-DEVI void list_candidate(const dprf_enum &e, uint32_t g, cand &c) {
-    const uint64_t slot = e.start + g;
-    const uint4 *s = (const uint4 *)(e.slots + slot * DPRF_SLOT_WORDS);
-#pragma unroll
-    for (int q = 0; q < DPRF_SLOT_WORDS / 4; q++) {
-        uint4 v = s[q];
-        c.w[4 * q + 0] = v.x; c.w[4 * q + 1] = v.y; c.w[4 * q + 2] = v.z; c.w[4 * q + 3] = v.w;
-    }
-    /* the host never packs more than a slot; the clamp keeps the message builders inside their arrays whatever
-     * the length byte holds */
-    const uint32_t len = e.lens[slot];
-    c.len = len < 4u * DPRF_SLOT_WORDS ? len : 4u * DPRF_SLOT_WORDS;
-}
-
-template <int MODE>
-DEVI void get_candidate(const dprf_enum &e, const uint8_t *cs, uint32_t g, cand &c) {
-    if (MODE == 0) range_candidate(e, cs, g, c);
-    else list_candidate(e, g, c);
-}
-
-/* Stage the charset (and the AES tables) into LDS and decide once per block whether it runs: with stop_on_first a
- * block is skipped only when its lowest candidate index lies above the lowest hit known so far (dprf_hits.h).  COUNT:
- * the check kernel counts the candidates it skips; the KDF kernel skips exactly the same blocks and does not. */
-template <bool AES, bool COUNT>
-DEVI bool block_prologue(const dprf_enum &e, const dprf_aes_tables *T, dprf_results *R, uint32_t stop_on_first,
-                         uint8_t *cs, aes_lds *L, uint32_t *flag) {
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t k = tid; k < 64; k += blockDim.x) ((uint32_t *)cs)[k] = ((const uint32_t *)e.charset)[k];
-    if (AES) {
-        for (uint32_t k = tid; k < 256; k += blockDim.x) { L->te[k] = T->te0[k]; L->td[k] = T->td0[k]; }
-        for (uint32_t k = tid; k < 64; k += blockDim.x) {
-            L->sb[k] = ((const uint32_t *)T->sbox)[k];
-            L->isb[k] = ((const uint32_t *)T->inv_sbox)[k];
-        }
-    }
-    if (tid == 0) {
-        uint32_t skip = 0u;
-        if (stop_on_first) {
-            const uint32_t off = blockIdx.x * blockDim.x;
-            skip = e.start + off > lowest_known(e, R) ? 1u : 0u;
-            if (skip && COUNT) {
-                const uint32_t n = e.count - off < blockDim.x ? e.count - off : blockDim.x;
-                atomicAdd(&R->skipped, (unsigned long long)n);
-            }
-        }
-        *flag = skip;
-    }
-    __syncthreads();
-    return *flag == 0;
-}
-
-/* BE message words of the candidate placed after the 16 salt bytes already in m[0..3], with the 0x80 terminator.
- * Static indices only.  A candidate that fills its whole 64-byte slot (32 UTF-16 units) has its terminator in the
- * word after the slot. */
-DEVI void be_append_salted(uint32_t m[32], const cand &c) {
-#pragma unroll
-    for (int j = 0; j < DPRF_SLOT_WORDS; j++)
-        m[4 + j] = bswap32((c.w[j] & le_keep_mask(j, c.len)) | le_pad80(j, c.len));
-#pragma unroll
-    for (int j = 4 + DPRF_SLOT_WORDS; j < 32; j++) m[j] = 0;
-    m[4 + DPRF_SLOT_WORDS] = c.len == 4u * DPRF_SLOT_WORDS ? 0x80000000u : 0u;
-}
-
 /* the two block keys of 2.3.4.13 as BE words */
 constexpr uint32_t BK1_HI = 0xfea7d276u, BK1_LO = 0x3b4b9e79u;   /* verifier hash input */
 constexpr uint32_t BK2_HI = 0xd7aa0f6du, BK2_LO = 0x3061344eu;   /* verifier hash value */
@@ -237,11 +148,11 @@ DEVI void agile_kdf_sha1(const dprf_enum &e, const dprf_agile_params &p, const u
     uint32_t h[5];
     {
         cand c;
-        get_candidate<MODE>(e, cs, g, c);
+        get_candidate<MODE, true>(e, cs, g, c);
         /* h = SHA1(salt || UTF16LE(pw)): 16 + up to 64 bytes, one or two blocks chosen per lane */
         uint32_t m[32];
         m[0] = p.salt[0]; m[1] = p.salt[1]; m[2] = p.salt[2]; m[3] = p.salt[3];
-        be_append_salted(m, c);
+        be_append<4>(m, c);
         const uint32_t total = 16u + c.len, bits = total * 8u;
         const bool two = total > 55u;
         uint32_t b0[16], b1[16];
@@ -283,11 +194,11 @@ DEVI void agile_kdf_sha512(const dprf_enum &e, const dprf_agile_params &p, const
     uint64_t h[8];
     {
         cand c;
-        get_candidate<MODE>(e, cs, g, c);
+        get_candidate<MODE, true>(e, cs, g, c);
         /* h = SHA512(salt || UTF16LE(pw)): at most 80 bytes, always one 128-byte block */
         uint32_t m[32];
         m[0] = p.salt[0]; m[1] = p.salt[1]; m[2] = p.salt[2]; m[3] = p.salt[3];
-        be_append_salted(m, c);
+        be_append<4>(m, c);
         uint64_t w[16];
 #pragma unroll
         for (int k = 0; k < 15; k++) w[k] = pack64(m[2 * k], m[2 * k + 1]);
@@ -416,8 +327,6 @@ k_agile_check(dprf_enum e, dprf_agile_params p, const dprf_aes_tables *T, dprf_r
 }
 
 /* ------------------------------------------------------------------ launcher */
-#define GRID(n, b) dim3(((n) + (b) - 1) / (b))
-
 hipError_t launch_agile(const dprf_enum &e, const dprf_agile_params &p, const dprf_aes_tables *T, dprf_results *R,
                         uint32_t cap, uint32_t stop, hipStream_t s, uint32_t *keys, hipEvent_t mid) {
     /* the host refuses Agile candidates longer than a slot: no long-list mode */

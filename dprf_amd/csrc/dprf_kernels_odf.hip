@@ -8,78 +8,14 @@
  * is checked against libcrypto (tests/test_odf_legacy_model.py).
  *
  * A translation unit of its own: the other kernel objects keep their machine code.  The candidate source and the block
- * prologue are restated from dprf_kernels.hip.
+ * prologue are dprf_cand.h's.
  */
 #include "dev_crypto.h"
 #include "dprf_params.h"
 #include "dprf_launch.h"
 #include "dprf_hits.h"
+#include "dprf_cand.h"
 #include "blowfish_init.h"
-
-namespace {
-/* ------------------------------------------------------------------ candidate source (as dprf_kernels.hip) */
-struct cand {
-    uint32_t w[DPRF_SLOT_WORDS];   /* LE-packed bytes */
-    uint32_t len;                  /* bytes */
-};
-
-/* Keyspace index start+g -> candidate in itertools.product order: the digit at position pwlen-1 varies fastest */
-DEVI void range_candidate(const dprf_enum &e, const uint8_t *cs, uint32_t g, cand &c) {
-#pragma unroll
-    for (int j = 0; j < DPRF_SLOT_WORDS; j++) c.w[j] = 0;
-    uint32_t rem = g, carry = 0;
-#pragma unroll
-    for (int p = DPRF_MAX_RANGE_LEN - 1; p >= 0; --p) {
-        if ((uint32_t)p < e.pwlen) {
-            uint32_t q = e.cslen == 1 ? rem : fastdiv(rem, e.div_m, e.div_s);
-            uint32_t r = rem - q * e.cslen;
-            uint32_t d = (uint32_t)e.sdig[p] + r + carry;
-            carry = d >= e.cslen ? 1u : 0u;
-            d -= carry ? e.cslen : 0u;
-            rem = q;
-            uint32_t ch = cs[d];
-            c.w[p >> 2] |= ch << (8 * (p & 3));
-        }
-    }
-    c.len = e.pwlen;
-}
-
-DEVI void list_candidate(const dprf_enum &e, uint32_t g, cand &c) {
-    const uint64_t slot = e.start + g;
-    const uint4 *s = (const uint4 *)(e.slots + slot * DPRF_SLOT_WORDS);
-#pragma unroll
-    for (int q = 0; q < DPRF_SLOT_WORDS / 4; q++) {
-        uint4 v = s[q];
-        c.w[4 * q + 0] = v.x; c.w[4 * q + 1] = v.y; c.w[4 * q + 2] = v.z; c.w[4 * q + 3] = v.w;
-    }
-    /* the host never packs more than a slot; the clamp keeps the message builder inside its array whatever the
-     * length byte holds */
-    const uint32_t len = e.lens[slot];
-    c.len = len < 4u * DPRF_SLOT_WORDS ? len : 4u * DPRF_SLOT_WORDS;
-}
-
-/* Decide once per block whether it runs: with stop_on_first a block is skipped only when its lowest candidate index
- * lies above the lowest hit known so far (dprf_hits.h).  COUNT: the check kernel counts the candidates it skips.  The
- * KDF kernel's blocks are whole multiples of the check kernel's and it looks at the lowest hit earlier, so every
- * candidate it skips the check kernel skips too: no check block reads a key that was not written. */
-template <bool COUNT>
-DEVI bool block_runs(const dprf_enum &e, dprf_results *R, uint32_t stop_on_first, uint32_t *flag) {
-    if (threadIdx.x == 0) {
-        uint32_t skip = 0u;
-        if (stop_on_first) {
-            const uint32_t off = blockIdx.x * blockDim.x;
-            skip = e.start + off > lowest_known(e, R) ? 1u : 0u;
-            if (skip && COUNT) {
-                const uint32_t n = e.count - off < blockDim.x ? e.count - off : blockDim.x;
-                atomicAdd(&R->skipped, (unsigned long long)n);
-            }
-        }
-        *flag = skip;
-    }
-    __syncthreads();
-    return *flag == 0;
-}
-}  // namespace
 
 /* ================================================================== KDF */
 /* k_odt_kdf's loop with one output block: the same two sha1_compress_pre per iteration, so the same registers and
@@ -93,8 +29,9 @@ __global__ void __launch_bounds__(ODF_KDF_THREADS, ODF_KDF_WAVES)
 k_odf_bf_kdf(dprf_enum e, dprf_odf_params p, dprf_results *R, uint32_t stop_on_first, uint32_t *keys) {
     __shared__ uint8_t cs[256];
     __shared__ uint32_t flag;
+    /* the charset is staged here, not by the prologue: in the prologue the same loop gets another schedule */
     for (uint32_t k = threadIdx.x; k < 64; k += blockDim.x) ((uint32_t *)cs)[k] = ((const uint32_t *)e.charset)[k];
-    if (!block_runs<false>(e, R, stop_on_first, &flag)) return;
+    if (!block_prologue<false, false, false>(e, nullptr, R, stop_on_first, cs, nullptr, &flag)) return;
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= e.count) return;
     /* start key = SHA1(password): one block up to 55 bytes, two from 56; a candidate that fills its 64-byte slot has
@@ -102,8 +39,7 @@ k_odf_bf_kdf(dprf_enum e, dprf_odf_params p, dprf_results *R, uint32_t stop_on_f
     uint32_t sk[5];
     {
         cand c;
-        if (MODE == 0) range_candidate(e, cs, g, c);
-        else list_candidate(e, g, c);
+        get_candidate<MODE, false>(e, cs, g, c);
         uint32_t b0[16], b1[16];
 #pragma unroll
         for (int j = 0; j < DPRF_SLOT_WORDS; j++) {
@@ -162,7 +98,9 @@ k_odf_bf_kdf(dprf_enum e, dprf_odf_params p, dprf_results *R, uint32_t stop_on_f
  * CFB decryption have constant inputs (iv and ciphertext) and are independent: they run eight at a time, one SHA-1
  * message block's worth, so that their lookups overlap. */
 #define ODF_BF_CANDS 32
-static_assert(ODF_KDF_THREADS % ODF_BF_CANDS == 0, "a KDF block is whole check blocks (block_runs)");
+/* The KDF kernel's blocks are whole multiples of the check kernel's and it looks at the lowest hit earlier, so every
+ * candidate it skips the check kernel skips too: no check block reads a key that was not written. */
+static_assert(ODF_KDF_THREADS % ODF_BF_CANDS == 0, "a KDF block is whole check blocks (block_prologue)");
 __shared__ uint32_t bf_box[1024 * ODF_BF_CANDS];
 __device__ const uint32_t bf_init[BF_INIT_WORDS] = BF_INIT_TABLE;
 
@@ -200,7 +138,7 @@ __global__ void __launch_bounds__(ODF_BF_CANDS)
 k_odf_bf_check(dprf_enum e, dprf_odf_params p, dprf_results *R, uint32_t cap, uint32_t stop_on_first,
                const uint32_t *keys) {
     __shared__ uint32_t flag;
-    if (!block_runs<true>(e, R, stop_on_first, &flag)) return;
+    if (!block_prologue<false, true, false>(e, nullptr, R, stop_on_first, nullptr, nullptr, &flag)) return;
     const uint32_t lane = threadIdx.x;
     const uint32_t g = blockIdx.x * blockDim.x + lane;
     if (lane >= ODF_BF_CANDS || g >= e.count) return;
@@ -254,8 +192,6 @@ k_odf_bf_check(dprf_enum e, dprf_odf_params p, dprf_results *R, uint32_t cap, ui
 }
 
 /* ------------------------------------------------------------------ launcher */
-#define GRID(n, b) dim3(((n) + (b) - 1) / (b))
-
 hipError_t launch_odf(const dprf_enum &e, const dprf_odf_params &p, dprf_results *R, uint32_t cap, uint32_t stop,
                       hipStream_t s_kdf, hipStream_t s_check, uint32_t *keys, hipEvent_t mid) {
     /* the host refuses candidates longer than a slot: no long-list mode */

@@ -15,86 +15,17 @@
  * box per lane) and one key wave that hashes the RC4 keys of batch b + 1 while the RC4 wave runs batch b; the keys
  * change hands through the S-box area between two barriers.  16,656 bytes of LDS per workgroup: 9 workgroups per CU.
  *
- * A translation unit of its own: the other kernel objects keep their machine code.  The candidate source and the
- * block prologue are restated from dprf_kernels.hip.
+ * A translation unit of its own: the other kernel objects keep their machine code.  The candidate source, the
+ * block prologue and be_append are dprf_cand.h's.
  */
 #include "dev_crypto.h"
 #include "dprf_params.h"
 #include "dprf_launch.h"
 #include "dprf_hits.h"
+#include "dprf_cand.h"
 #include "rc4_dev.h"
 
 namespace {
-/* ------------------------------------------------------------------ candidate source (as dprf_kernels.hip) */
-struct cand {
-    uint32_t w[DPRF_SLOT_WORDS];   /* LE-packed UTF-16LE code units */
-    uint32_t len;                  /* bytes */
-};
-
-/* Keyspace index start+g -> candidate in itertools.product order, as UTF-16LE code units (ASCII charset only) */
-DEVI void range_candidate(const dprf_enum &e, const uint8_t *cs, uint32_t g, cand &c) {
-#pragma unroll
-    for (int j = 0; j < DPRF_SLOT_WORDS; j++) c.w[j] = 0;
-    uint32_t rem = g, carry = 0;
-#pragma unroll
-    for (int p = DPRF_MAX_RANGE_LEN - 1; p >= 0; --p) {
-        if ((uint32_t)p < e.pwlen) {
-            uint32_t q = e.cslen == 1 ? rem : fastdiv(rem, e.div_m, e.div_s);
-            uint32_t r = rem - q * e.cslen;
-            uint32_t d = (uint32_t)e.sdig[p] + r + carry;
-            carry = d >= e.cslen ? 1u : 0u;
-            d -= carry ? e.cslen : 0u;
-            rem = q;
-            uint32_t ch = cs[d];
-            c.w[p >> 1] |= ch << (16 * (p & 1));
-        }
-    }
-    c.len = 2 * e.pwlen;
-}
-
-DEVI void list_candidate(const dprf_enum &e, uint32_t g, cand &c) {
-    const uint64_t slot = e.start + g;
-    const uint4 *s = (const uint4 *)(e.slots + slot * DPRF_SLOT_WORDS);
-#pragma unroll
-    for (int q = 0; q < DPRF_SLOT_WORDS / 4; q++) {
-        uint4 v = s[q];
-        c.w[4 * q + 0] = v.x; c.w[4 * q + 1] = v.y; c.w[4 * q + 2] = v.z; c.w[4 * q + 3] = v.w;
-    }
-    /* the host never packs more than a slot; the clamp keeps the message builders inside their arrays whatever
-     * the length byte holds */
-    const uint32_t len = e.lens[slot];
-    c.len = len < 4u * DPRF_SLOT_WORDS ? len : 4u * DPRF_SLOT_WORDS;
-}
-
-template <int MODE>
-DEVI void get_candidate(const dprf_enum &e, const uint8_t *cs, uint32_t g, cand &c) {
-    if (MODE == 0) range_candidate(e, cs, g, c);
-    else list_candidate(e, g, c);
-}
-
-/* Stage the charset into LDS and decide once per block whether it runs: with stop_on_first a block is skipped only
- * when its lowest candidate index lies above the lowest hit known so far (dprf_hits.h).  per: candidates per thread of
- * the block. */
-DEVI bool block_prologue(const dprf_enum &e, dprf_results *R, uint32_t stop_on_first, uint8_t *cs, uint32_t *flag,
-                         uint32_t per) {
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t k = tid; k < 64; k += blockDim.x) ((uint32_t *)cs)[k] = ((const uint32_t *)e.charset)[k];
-    if (tid == 0) {
-        uint32_t skip = 0u;
-        if (stop_on_first) {
-            const uint32_t off = blockIdx.x * blockDim.x * per;
-            skip = e.start + off > lowest_known(e, R) ? 1u : 0u;
-            if (skip) {
-                const uint32_t n = e.count - off < blockDim.x * per ? e.count - off : blockDim.x * per;
-                atomicAdd(&R->skipped, (unsigned long long)n);
-            }
-        }
-        *flag = skip;
-    }
-    __syncthreads();
-    return *flag == 0;
-}
-
 /* ------------------------------------------------------------------ RC4 key of one candidate */
 /* Types 0 / 1: nine MD5 compressions at most (the first message is one block up to 27 characters, two from 28). */
 DEVI void key_md5(const dprf_oldoffice_params &p, const cand &c, uint32_t k[4]) {
@@ -157,12 +88,7 @@ DEVI void key_sha1(const dprf_oldoffice_params &p, const cand &c, uint32_t k[4])
     {
         uint32_t m[32];
         m[0] = p.salt[0]; m[1] = p.salt[1]; m[2] = p.salt[2]; m[3] = p.salt[3];
-#pragma unroll
-        for (int j = 0; j < DPRF_SLOT_WORDS; j++)
-            m[4 + j] = bswap32((c.w[j] & le_keep_mask(j, c.len)) | le_pad80(j, c.len));
-#pragma unroll
-        for (int j = 4 + DPRF_SLOT_WORDS; j < 32; j++) m[j] = 0;
-        m[4 + DPRF_SLOT_WORDS] = c.len == 4u * DPRF_SLOT_WORDS ? 0x80000000u : 0u;
+        be_append<4>(m, c);
         const uint32_t total = 16u + c.len, bits = total * 8u;
         const bool two = total > 55u;
         uint32_t b0[16], b1[16];
@@ -197,7 +123,7 @@ template <int MODE, bool SHA1>
 DEVI void oldoffice_key(const dprf_enum &e, const dprf_oldoffice_params &p, const uint8_t *cs, uint32_t g,
                         uint32_t k[4]) {
     cand c;
-    get_candidate<MODE>(e, cs, g, c);
+    get_candidate<MODE, true>(e, cs, g, c);
     if (SHA1) key_sha1(p, c, k);
     else key_md5(p, c, k);
 }
@@ -230,7 +156,7 @@ k_oldoffice(dprf_enum e, dprf_oldoffice_params p, dprf_results *R_, uint32_t cap
     __shared__ __attribute__((aligned(16))) uint32_t aux[64 + 4];
     uint8_t *cs = (uint8_t *)aux;                         /* charset, 256 B */
     uint32_t *flag = aux + 64;
-    if (!block_prologue(e, R_, stop_on_first, cs, flag, NBAT / 2)) return;
+    if (!block_prologue<false>(e, nullptr, R_, stop_on_first, cs, nullptr, flag, NBAT / 2)) return;
     const uint32_t base = blockIdx.x * (64u * NBAT);
     const uint32_t left = e.count - base;                 /* > 0: grid = ceil(count / (64 * NBAT)) */
     const uint32_t nb = left >= 64u * NBAT ? (uint32_t)NBAT : (left + 63u) / 64u;

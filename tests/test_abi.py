@@ -71,6 +71,29 @@ def test_makefile_tracks_every_local_header():
                 assert inc in hdrs, (f, inc)
 
 
+def test_candidate_source_is_defined_once():
+    """dprf_cand.h is the only definition of the candidate source and the block prologue: the enumeration order, the
+    lowest-hit rule and the full-slot terminator were each a bug once, and four hand-kept copies had drifted."""
+    csrc = os.path.join(REPO, "dprf_amd", "csrc")
+    text = dict((f, open(os.path.join(csrc, f)).read()) for f in sorted(os.listdir(csrc))
+                if f.endswith((".hip", ".cpp", ".h")))
+    assert "dprf_cand.h" in text
+    # a definition: `struct cand {`, or the name after a return type at the start of a line (a call is indented)
+    defs = {"struct cand": r"^\s*struct\s+cand\b[^;]*\{"}
+    for name in ("range_candidate", "list_candidate", "block_prologue"):
+        defs[name] = r"^(?:DEVI|__device__|static|inline)[^;(]*\b%s\s*\(" % name
+    for what, pat in defs.items():
+        where = [(f, len(re.findall(pat, src, re.M))) for f, src in text.items() if re.search(pat, src, re.M)]
+        assert where == [("dprf_cand.h", 1)], (what, where)
+    for f, src in text.items():
+        if not f.endswith(".hip"):
+            continue
+        for gone in ("block_runs", "be_append_salted"):      # the renamed copies: neither defined nor called
+            assert not re.search(r"\b%s\s*[<(]" % gone, src), (f, gone)
+        if re.search(r"\bget_candidate\s*<", src):
+            assert re.search(r'^#include "dprf_cand\.h"', src, re.M), f
+
+
 def test_ctypes_structs_match_the_header_layout(tmp_path):
     """dprf_stats / dprf_device_stats as a C compiler lays them out (include/dprf.h) == the ctypes mirrors (ABI 6
     appended hit_ms and evaluated): sizes and every field offset."""
