@@ -94,6 +94,25 @@ def test_candidate_source_is_defined_once():
             assert re.search(r'^#include "dprf_cand\.h"', src, re.M), f
 
 
+def test_family_table_is_the_one_place_that_knows_a_family():
+    """What the host knows of a kernel family is one row of FAMILIES in dprf_doc.cpp: every family name is written once
+    in the host sources, the per-family refusal sentences live in the document unit only, and that unit is free of
+    HIP, so a plain C++ compiler builds it (tests/test_doc_layer.py does)."""
+    csrc = os.path.join(REPO, "dprf_amd", "csrc")
+    text = dict((f, open(os.path.join(csrc, f)).read()) for f in sorted(os.listdir(csrc)) if f.endswith((".cpp", ".h")))
+    names = ["office_std", "odf_aes256", "odf_bf_sha1", "office_agile_sha1", "office_agile_sha512", "office_rc4_md5",
+             "office_rc4_sha1", "pdf_r24", "pdf_r5", "pdf_r6", "pdf_r24_owner", "pdf_r5_owner", "pdf_r6_owner"]
+    for name in names:
+        where = [(f, src.count('"%s"' % name)) for f, src in text.items() if '"%s"' % name in src]
+        assert where == [("dprf_doc.cpp", 1)], (name, where)
+    for f in ("dprf_doc.cpp", "dprf_doc.h"):
+        assert not re.search(r"\bhip", text[f], re.I), f                # hipMalloc, hip_runtime.h, HIPCHK, "HIP"
+    assert [f for f, src in text.items() if "not supported yet" in src] == ["dprf_doc.cpp"]
+    # the per-kind helpers are gone from the device half, which asks status_text for a sentence and holds none
+    for gone in ("is_agile", "is_oldoffice", "slot_trunc", "two_kernels", "key_words(", "*status_text", "*kind_name"):
+        assert gone not in text["dprf_host.cpp"], gone
+
+
 def test_ctypes_structs_match_the_header_layout(tmp_path):
     """dprf_stats / dprf_device_stats as a C compiler lays them out (include/dprf.h) == the ctypes mirrors (ABI 6
     appended hit_ms and evaluated): sizes and every field offset."""

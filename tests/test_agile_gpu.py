@@ -184,27 +184,39 @@ def _serves(dprf, s):
         assert ctx.verify_list([PW, "Ux8"])[0] == [0]
 
 
-def test_stream_refusals(dprf):
+def refusal_base():
+    """The stream the refused ones are made from, and its fields."""
     good = _stream(PW, "2013", 256, 1000)
-    base = _fields(good)
-    bad = {
-        "keyBits 192": (3, "192"),
-        "saltSize 8": (4, "8"),
-        "spinCount 10,000,001": (2, "10000001"),
-        "30-digit verifier input": (6, base[6][:30]),
+    return good, _fields(good)
+
+
+def bad_streams(base):
+    """What is refused, as changes to `base`: label -> (field index, value, the field name the message carries or
+    None).  tests/test_doc_layer.py runs the same list through the document layer without a device."""
+    return {
+        "keyBits 192": (3, "192", "keyBits"),
+        "saltSize 8": (4, "8", "saltSize"),
+        "spinCount 10,000,001": (2, "10000001", "spinCount"),
+        "30-digit verifier input": (6, base[6][:30], "encryptedVerifierHashInput"),
         # any version but "2010" / "2013" is read as the 2007 stream, where field 2 is the verifier hash size: 1000
         # lies outside it
-        "version 2016": (1, "2016"),
+        "version 2016": (1, "2016", None),
     }
-    for what, (k, v) in bad.items():
+
+
+def test_stream_refusals(dprf):
+    good, base = refusal_base()
+    bad = bad_streams(base)
+    for what, (k, v, _) in bad.items():
         f = list(base)
         f[k] = v
         with pytest.raises(dprf.DprfError) as ei:
             dprf.Context(f, device=0)
         assert ei.value.code == dprf.E_DOMAIN, what
         _serves(dprf, good)
-    for k, v, name in ((3, "192", "keyBits"), (4, "8", "saltSize"), (2, "10000001", "spinCount"),
-                       (6, base[6][:30], "encryptedVerifierHashInput")):
+    for k, v, name in bad.values():
+        if name is None:
+            continue
         f = list(base)
         f[k] = v
         with pytest.raises(dprf.DprfError) as ei:

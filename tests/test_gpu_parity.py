@@ -285,8 +285,18 @@ def test_errors_are_errors_not_hits(dprf, streams):
         c2.search_range(LOWER, 3, 26 ** 3 - 5, 10)
 
 
+# a (V, R) pair outside the reference's whitelist: its verify() answers 0 for every candidate
+NEVER_MATCHING = ["pdf", "2", "4", "128", "-4", "1", "16", "11" * 16, "32", "22" * 32, "32", "33" * 32]
+# streams outside the parity domain (DPRF_E_DOMAIN): an ODT ciphertext length that is no multiple of 16, an R3 key of 8
+# bytes; tests/test_doc_layer.py runs the same two through the document layer without a device
+DOMAIN_STREAMS = [
+    ["odt", "1.2", "11" * 32, "22" * 16, "33" * 16, "44" * 17, "17"],
+    ["pdf", "2", "3", "64", "-4", "1", "16", "11" * 16, "32", "22" * 32, "32", "33" * 32],
+]
+
+
 def test_never_matches_and_empty_inputs(dprf):
-    f = ["pdf", "2", "4", "128", "-4", "1", "16", "11" * 16, "32", "22" * 32, "32", "33" * 32]
+    f = NEVER_MATCHING
     c = dprf.Context(f)
     assert c.flags & dprf.FLAG_NEVER_MATCHES
     hits, n, st = c.search_range(LOWER, 3, 0, 26 ** 3)
@@ -297,12 +307,10 @@ def test_never_matches_and_empty_inputs(dprf):
 
 
 def test_domain_streams_rejected(dprf):
-    with pytest.raises(dprf.DprfError) as ei:
-        dprf.Context(["odt", "1.2", "11" * 32, "22" * 16, "33" * 16, "44" * 17, "17"])
-    assert ei.value.code == dprf.E_DOMAIN
-    with pytest.raises(dprf.DprfError) as ei:
-        dprf.Context(["pdf", "2", "3", "64", "-4", "1", "16", "11" * 16, "32", "22" * 32, "32", "33" * 32])
-    assert ei.value.code == dprf.E_DOMAIN
+    for f in DOMAIN_STREAMS:
+        with pytest.raises(dprf.DprfError) as ei:
+            dprf.Context(f)
+        assert ei.value.code == dprf.E_DOMAIN, f
 
 
 def test_many_hits_overflow_and_order(dprf, streams, hitsets):

@@ -44,7 +44,7 @@ def test_odt_parser_matches_golden(streams):
 
 
 def _fastdiv(n, d):
-    """The u32 division the kernels use (dev_crypto.h fastdiv) with the host magic (dprf_host.cpp)."""
+    """The u32 division the kernels use (dev_crypto.h fastdiv) with the host magic (dprf_doc.cpp)."""
     if d <= 1:
         return n
     l = (d - 1).bit_length()

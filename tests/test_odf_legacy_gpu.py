@@ -264,10 +264,16 @@ def _serves(dprf, s):
         assert ctx.verify_list([PW, "Ux8"])[0] == [0]
 
 
-def test_stream_refusals(dprf):
+def refusal_base():
+    """The stream the refused ones are made from, and its fields."""
     good = _stream(PW)
-    base = _fields(good)
-    bad = [
+    return good, _fields(good)
+
+
+def bad_streams(base):
+    """What is refused with DPRF_E_DOMAIN, as changes to `base`: (what the message carries, then field index and value,
+    once or twice).  tests/test_doc_layer.py runs the same list through the document layer without a device."""
+    return [
         ("cipher", 1, "2"), ("$odt$", 1, "1", 2, "1"), ("checksum type", 2, "1"), ("key size", 4, "32"),
         ("iv length", 6, "16"), ("salt length", 8, "32"), ("inplace", 10, "1"),
         ("iterations", 3, "0"), ("iterations", 3, "10000001"), ("iterations", 3, ""), ("iterations", 3, "1k"),
@@ -277,6 +283,11 @@ def test_stream_refusals(dprf):
         ("salt", 9, base[9] + "ab"), ("salt", 9, base[9][:-1] + "z"),
         ("content", 11, base[11][:-16]), ("content", 11, base[11] + "00"), ("content", 11, base[11][:100] + "q" + base[11][101:]),
     ]
+
+
+def test_stream_refusals(dprf):
+    good, base = refusal_base()
+    bad = bad_streams(base)
     for name, *changes in bad:
         f = list(base)
         for k, v in zip(changes[0::2], changes[1::2]):

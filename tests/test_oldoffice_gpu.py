@@ -231,11 +231,19 @@ def _serves(dprf, s):
         assert ctx.verify_list([PW, "Ux8"])[0] == [0]
 
 
-@pytest.mark.parametrize("typ", [1, 3])
-def test_stream_refusals(dprf, typ):
+REFUSAL_TYPES = [1, 3]
+
+
+def refusal_base(typ):
+    """The stream the refused ones are made from, and its fields."""
     good = _stream(PW, typ)
-    base = _fields(good)
-    bad = [
+    return good, _fields(good)
+
+
+def bad_streams(base):
+    """What is refused with DPRF_E_DOMAIN, as changes to `base`: (the field name the message carries, field index,
+    value).  tests/test_doc_layer.py runs the same list through the document layer without a device."""
+    return [
         ("type", 1, "2"), ("type", 1, "5"), ("type", 1, ""), ("type", 1, "01"),
         ("salt", 2, base[2][:30]), ("salt", 2, base[2] + "00"), ("salt", 2, "g" + base[2][1:]),
         ("encryptedVerifier", 3, base[3][:-2]), ("encryptedVerifier", 3, base[3] + "ab"),
@@ -243,6 +251,12 @@ def test_stream_refusals(dprf, typ):
         ("encryptedVerifierHash", 4, base[4][:-8]), ("encryptedVerifierHash", 4, base[4] + "00000000"),
         ("encryptedVerifierHash", 4, base[4][:-1] + "z"),
     ]
+
+
+@pytest.mark.parametrize("typ", REFUSAL_TYPES)
+def test_stream_refusals(dprf, typ):
+    good, base = refusal_base(typ)
+    bad = bad_streams(base)
     for name, k, v in bad:
         f = list(base)
         f[k] = v

@@ -203,11 +203,18 @@ def test_owner_mode_is_pdf_only(dprf, streams):
         assert dprf.lib().dprf_ctx_set_pdf_password(ctx._h, 7) == dprf.E_INVALID and ctx.pdf_password == "user"
 
 
+def short_u_fields():
+    """The R6 golden document with U cut to the 40 bytes the user check needs: the owner check, which reads 48, is out
+    of domain on it.  tests/test_doc_layer.py runs the same fields through the document layer without a device."""
+    fields = _fields(_stream("pdf_r6.pdf"))
+    assert fields[8] == "48" and len(fields[9]) == 96
+    fields[8], fields[9] = "40", fields[9][:80]
+    return fields
+
+
 def test_short_u_is_out_of_domain_and_user_mode_survives(dprf):
     e = _docs()["pdf_r6.pdf"]
-    fields = _fields(e["streams"]["std"]["stream"])
-    assert fields[8] == "48" and len(fields[9]) == 96
-    fields[8], fields[9] = "40", fields[9][:80]                             # the user check needs 40 bytes of U only
+    fields = short_u_fields()
     pw = e["password"]
     idx = M.index_of(pw, LOWER)
     with dprf.Context(fields, device=0) as ctx:

@@ -25,7 +25,7 @@ NO_TRUNC = M32            # dprf_search_symbols: 32 for PDF R2-R4, 127 for R5, ~
 
 # ------------------------------------------------------------------ host side (dprf_host.cpp)
 def utf8_to_utf16le(s):
-    """utf8_to_utf16le of dprf_host.cpp for one valid character: code point by shifts, surrogates by arithmetic."""
+    """utf8_to_utf16le of dprf_doc.cpp for one valid character: code point by shifts, surrogates by arithmetic."""
     b = s[0]
     if b < 0x80:
         cp, k = b, 1

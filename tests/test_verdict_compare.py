@@ -241,7 +241,7 @@ U_PW, U_LONG32, U_LONG64 = "Tq8$z", "Tq8$z" * 8, "Tq8$z" * 14          # 5, 40 (
 O_PW, O_LONG32 = "Ow7", "Ow7#k" * 8
 
 CITE_R24 = ("dprf_kernels.hip launch_pdf_r24 (declared in dprf_launch.h): e.mode 0 -> k_pdf_r24<0, ..>, the list "
-            "-> <1, ..>; dprf_host.cpp convert_candidate: `kind == K_PDF_R24 && len > 32` -> 32 bytes, so the word "
+            "-> <1, ..>; dprf_doc.cpp convert_candidate: the pdf_r24 row of FAMILIES cuts at 32 bytes, so the word "
             "stays in the slot sub-list of dprf_verify_list")
 CITE_R5 = ("dprf_kernels.hip launch_pdf_r5 (dprf_launch.h): L5W picks runs of 16 for e.cslen >= 16, else PER 8, and "
            "k_pdf_r5 takes the run path only when e.cslen >= PER; list launches: e.pwlen <= 8 -> L5(1, 2, 8), "
@@ -744,7 +744,7 @@ def test_collision_documents_on_the_cpu(inst, rel, owner):
         assert M.owner_verifies(stream, A.word(a, cs, n)) and not M.owner_verifies(stream, A.word(b, cs, n))
     else:
         assert O.Ctx(stream).verify(A.word(b, cs, n)) == 0
-    # one launch on one device, so batches and workgroups count from `start` (dprf_host.cpp policy / plan_chunk:
+    # one launch on one device, so batches and workgroups count from `start` (dprf_doc.cpp policy / plan_chunk:
     # K_PDF_R24's first chunk is 2^24, halved for the owner kernels)
     assert _lib.plan_chunk("pdf_r24_owner" if owner else "pdf_r24", 0.0, count, count, 1) == count
     want_rel = {"both-survive": ("same-batch",), "odd-start": ("batch-before", "batch-after"),
