@@ -16,7 +16,7 @@
 #include "dprf_launch.h"
 #include "dprf_hits.h"
 #include "dprf_cand.h"
-#include "rc4_dev.h"
+#include "rc4_wg.h"
 
 /* The candidate source, the block prologue and be_append are dprf_cand.h's.  The kernels of this file read a list
  * candidate's length byte unclamped (get_candidate<MODE, UTF16, LIST_CLAMP>): the four objects built from it are the
@@ -672,242 +672,30 @@ k_pdf_r5(dprf_enum e, dprf_pdf_params p, dprf_results *R, uint32_t cap, uint32_t
 }
 
 /* ================================================================== PDF R2..R4 (MD5 + RC4) */
-/* RC4 S-box layout, KSA and PRGA: rc4_dev.h */
+/* RC4 S-box layout, KSA and PRGA: rc4_dev.h; the two-wave workgroup and its driver: rc4_wg.h */
 
-/* RC4 key of candidate g: MD5(pw[:32] || PAD[0:32-len] || O || LE32(P) || ID [|| FFFFFFFF]) (pdf...c:136-139,
- * :352-402), then 50 x MD5(h[0:n]) for R >= 3 (:150-155).  Reads the charset and PAD from the LDS overlay. */
-template <int MODE, int R, int NK>
-DEVI void r24_key(const dprf_enum &e, const dprf_pdf_params &p, const uint8_t *cs, const uint32_t *padw,
-                  const uint32_t padtail[8], uint32_t g, uint32_t h[4]) {
-    cand c;
-    get_candidate<MODE, false, LIST_CLAMP>(e, cs, g, c);
-    const uint32_t len = c.len > 32u ? 32u : c.len;
-    uint32_t pw[8];
+/* Range mode: pwlen <= 32 and a candidate's bytes past it are zero, so PAD at byte offset pwlen is launch-uniform:
+ * eight words built once per key wave and OR-ed onto every candidate.  List mode reads PAD per lane: zeros here. */
+template <int MODE>
+DEVI void r24_padtail(const dprf_enum &e, const dprf_pdf_params &p, uint32_t padtail[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) padtail[j] = 0u;
     if (MODE == 0) {
-        /* range mode: pwlen <= 32 and the bytes past it are zero; PAD at offset pwlen is launch-uniform */
+        const uint32_t q = e.pwlen >> 2, r = (e.pwlen & 3u) * 8u;
 #pragma unroll
-        for (int j = 0; j < 8; j++) pw[j] = c.w[j] | padtail[j];
-    } else {
+        for (int t = 0; t < 8; t++) {
+            const uint32_t lo = r ? (p.pad[t] << r) : p.pad[t];
+            const uint32_t hi = r ? (p.pad[t] >> (32u - r)) : 0u;
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            uint32_t v = c.w[j] & le_keep_mask(j, len);
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const uint32_t k = 4u * j + b;
-                if (k >= len) v |= (uint32_t)((const uint8_t *)padw)[k - len] << (8 * b);
+            for (int j = 0; j < 8; j++) {
+                if ((uint32_t)j == q + t) padtail[j] |= lo;
+                if ((uint32_t)j == q + t + 1) padtail[j] |= hi;
             }
-            pw[j] = v;
-        }
-    }
-    {
-        uint32_t m[16];
-#pragma unroll
-        for (int j = 0; j < 8; j++) { m[j] = pw[j]; m[8 + j] = p.tail[j]; }
-        md5_iv(h);
-        md5_compress(h, m);
-        for (uint32_t b = 0; b < p.tail_blocks; b++) {
-#pragma unroll
-            for (int j = 0; j < 16; j++) m[j] = p.tail[8 + 16 * b + j];
-            md5_compress(h, m);
-        }
-    }
-    if (R >= 3) {
-        for (int i = 0; i < 50; i++) {
-            uint32_t m[16];
-            if (NK == 16) {
-                m[0] = h[0]; m[1] = h[1]; m[2] = h[2]; m[3] = h[3]; m[4] = 0x80u;
-#pragma unroll
-                for (int j = 5; j < 16; j++) m[j] = 0u;
-                m[14] = 128u;
-            } else {
-                m[0] = h[0]; m[1] = (h[1] & 0xffu) | 0x8000u;
-#pragma unroll
-                for (int j = 2; j < 16; j++) m[j] = 0u;
-                m[14] = 40u;
-            }
-            md5_iv(h);
-            md5_compress(h, m);
         }
     }
 }
-
-/* One workgroup = one RC4 wave + one key wave, over NBAT batches of 64 candidates (round 2).
- *
- * The RC4 wave owns the workgroup's 16 KiB S-box area (one 256-byte box per lane) and only ever runs KSAs and
- * PRGAs; the key wave derives the RC4 keys (enumeration + MD5 of the padded password and document tail, and for
- * R3/R4 the 50 MD5 iterations) of batch b+1 while the RC4 wave runs batch b.  Keys are handed over through the
- * S-box area while it is free, between two barriers at each batch boundary; charset, PAD and the skip flag sit
- * in an area of their own (16,720 B per workgroup: still 9 per CU).  The RC4 wave raises its issue priority
- * (s_setprio 3), so the MD5s take only the VALU cycles the KSA chains leave free.
- * Why: when one wave did both (round 1 - mid round 2), a wave hashing its keys held its S-box without running
- * a KSA -- ~8 % of the CU's 9 KSA chains idle for R3/R4, ~15 % for R2.  Measured (tools/ab_libs.sh, MI355X):
- * R3/R4 fused 464 M, split without / with the priority 458 / 481 M; a key wave that hashes nothing (probe) 484 M,
- * so the MD5s are fully hidden; then the KSA group size re-tuned (rc4_ksa): R3/R4 513 M, R2 8.77 -> 9.79 G.
- * Batches per workgroup, R3/R4: 2 / 4 / 8 = 472 / 480 / 481 M (G = 4), 6 / 8 / 12 = 513 / 513 / 507 M (G = 2);
- * R2: 8 / 16 / 24 = 9.58 / 9.68 / 9.70 G.  Re-measured on the group-deferred KSA: R3/R4 6 / 8 / 12 batches
- * 559 / 560 / 557 M, priority 0 / 1 / 3 529 / 560 / 560 M; R2 8 / 16 / 24 batches 11.08 / 11.25 / 11.32 G,
- * priority 0 10.56 G.  Round 3 (asm KSA): 8 / 12 / 16 = 613 / 608 / 603 M; round 4, with consecutive launches on two
- * streams (the last partial generation of one launch overlaps the next): 8 / 12 / 16 = 626.2 / 628.5 / 625.2 M (three
- * alternating runs each, every run of 12 above the neighbouring 8), so 12.  R2 likewise: 16 / 24 / 36 / 48 = 12.23 /
- * 12.27 / 12.32 / 12.31 G, so 36 (profiles/ab_r2_batches_r04l.txt). */
-#ifndef R34_BATCHES
-#define R34_BATCHES 12
-#endif
-#ifndef R2_BATCHES
-#define R2_BATCHES 36
-#endif
-#ifndef R24_PRIO
-#define R24_PRIO 3
-#endif
-/* 1: the KSA as the generated asm block (rc4_dev.h rc4_ksa_asm); 0: the C++ rc4_ksa (A/B builds) */
-#ifndef R24_KSA_ASM
-#define R24_KSA_ASM 1
-#endif
-template <int NK>
-DEVI void r24_ksa(uint8_t *S, uint32_t sbase, uint32_t lane, const uint32_t k[4]) {
-    if (R24_KSA_ASM) rc4_ksa_asm<NK>(sbase, sbase + (lane << 2), k);
-    else rc4_ksa<NK>(S, lane << 2, k);
-}
-template <int R> struct r24_batches { static constexpr uint32_t v = R == 2 ? R2_BATCHES : R34_BATCHES; };
-template <int MODE, int R, int NK>
-__global__ void __launch_bounds__(128, 5)   /* 18 waves per CU (9 workgroups): <= 102 VGPRs */
-k_pdf_r24(dprf_enum e, dprf_pdf_params p, dprf_results *R_, uint32_t cap, uint32_t stop_on_first) {
-    constexpr uint32_t NBAT = r24_batches<R>::v;
-    static_assert(NBAT % 2 == 0, "block_prologue counts NBAT / 2 candidates per thread of the 128-thread block");
-    __shared__ __attribute__((aligned(16))) uint8_t S[RC4_WAVE_BYTES];
-    __shared__ __attribute__((aligned(16))) uint32_t aux[64 + 16 + 4];
-    uint8_t *cs = (uint8_t *)aux;                         /* charset, 256 B */
-    uint32_t *padw = aux + 64;                            /* PAD || PAD */
-    uint32_t *flag = aux + 80;
-    if (threadIdx.x < 8) { padw[threadIdx.x] = p.pad[threadIdx.x]; padw[threadIdx.x + 8] = p.pad[threadIdx.x]; }
-    /* per = candidates per thread of the 128-thread block: 64 * NBAT candidates */
-    if (!block_prologue<false>(e, nullptr, R_, stop_on_first, cs, nullptr, flag, NBAT / 2)) return;
-    const uint32_t base = blockIdx.x * (64u * NBAT);
-    const uint32_t left = e.count - base;                 /* > 0: grid = ceil(count / (64 * NBAT)) */
-    const uint32_t nb = left >= 64u * NBAT ? (uint32_t)NBAT : (left + 63u) / 64u;
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t *keyx = (uint32_t *)S;                       /* [4][64] words, only between the two barriers */
-    if (threadIdx.x >= 64u) {
-        /* key wave */
-        uint32_t padtail[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) padtail[j] = 0u;
-        if (MODE == 0) {
-            const uint32_t q = e.pwlen >> 2, r = (e.pwlen & 3u) * 8u;
-#pragma unroll
-            for (int t = 0; t < 8; t++) {
-                const uint32_t lo = r ? (p.pad[t] << r) : p.pad[t];
-                const uint32_t hi = r ? (p.pad[t] >> (32u - r)) : 0u;
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    if ((uint32_t)j == q + t) padtail[j] |= lo;
-                    if ((uint32_t)j == q + t + 1) padtail[j] |= hi;
-                }
-            }
-        }
-        uint32_t h[4];
-        {
-            const uint32_t g0 = base + lane;
-            r24_key<MODE, R, NK>(e, p, cs, padw, padtail, g0 < e.count ? g0 : e.count - 1, h);
-        }
-#pragma unroll 1
-        for (uint32_t b = 0; b < nb; b++) {
-            __syncthreads();                              /* the RC4 wave is done with batch b-1's S-box */
-#pragma unroll
-            for (int q = 0; q < 4; q++) keyx[64 * q + lane] = h[q];
-            __syncthreads();                              /* batch b's keys are in LDS */
-            if (b + 1u < nb) {
-                const uint32_t g0 = base + 64u * (b + 1u) + lane;
-                r24_key<MODE, R, NK>(e, p, cs, padw, padtail, g0 < e.count ? g0 : e.count - 1, h);
-            }
-        }
-        return;
-    }
-    /* RC4 wave */
-    __builtin_amdgcn_s_setprio(R24_PRIO);
-    uint8_t *Sw = S;
-    /* the asm KSA needs the S-box area at an LDS address with zero low 16 bits (rc4_ksa_asm); S is this kernel's
-     * first LDS object, at 0 -- checked, and a launch that ever breaks it fails loudly instead of computing wrong */
-    const uint32_t sbase = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) uint8_t *)S);
-    if (R24_KSA_ASM && (sbase & 0xffffu) != 0u) {
-        if (lane == 0) atomicOr(&R_->pad_, 2u);
-        for (uint32_t b = 0; b < nb; b++) { __syncthreads(); __syncthreads(); }   /* keep the key wave's barriers */
-        return;
-    }
-#pragma unroll 1
-    for (uint32_t b = 0; b < nb; b++) {
-        __syncthreads();
-        __syncthreads();
-        uint32_t h[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) h[q] = keyx[64 * q + lane];
-        /* the lane index recomputed here (v_mbcnt, opaque so LLVM cannot hoist base + lane out of the loop): a
-         * register holding it across the KSAs was the one value this kernel spilled to scratch */
-        uint32_t lid;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lid));
-        const uint32_t g = base + 64u * b + lid;
-        const bool valid = g < e.count;
-        bool ok = false;
-        if (R == 2) {
-            /* RC4-40 over PAD, compare 32 bytes of U (:161-163, :184-189).  The first 4 keystream bytes decide
-             * for all but 2^-32 of the lanes: a wave continues the same keystream (i = 5.., j carried) only
-             * when one of its lanes matches U[0:4] */
-            uint32_t d[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) d[j] = p.pad[j];
-            r24_ksa<5>(Sw, sbase, lane, h);
-            uint32_t jj = 0;
-            rc4_prga_span<1, 4>(Sw, lane << 2, d, jj);
-            if (__builtin_amdgcn_ballot_w64(valid && d[0] == p.u[0])) {
-                rc4_prga_span<5, 32>(Sw, lane << 2, d, jj);
-                ok = true;
-#pragma unroll
-                for (int j = 0; j < 8; j++) ok = ok && d[j] == p.u[j];
-            }
-        } else
-        /* c = RC4(key, MD5(PAD||ID)); c = RC4(key ^ x, c) for x = 1..19 (:167-174), compare 16 bytes.  Early
-         * reject: every pass first produces only 2 keystream bytes and the candidate survives iff c19[0:2]
-         * equals U[0:2]; a wave in which some lane survives (2^-16 per lane) redoes its candidates with the full
-         * keystream and the reference's complete 16-byte compare (:184-189) */
-        for (uint32_t full = 0; full < 2u; full++) {
-            uint32_t d[4] = {p.h2[0], p.h2[1], p.h2[2], p.h2[3]};
-            /* the asm KSA's key registers, made once per candidate; pass x's key (key ^ x) by XORing x ^ (x - 1)
-             * into their byte 0 (16 v_xor per pass, the same count as forming kx and extracting its bytes) */
-            uint32_t kb[NK];
-            rc4_kb_init<NK>(h, kb);
-            for (uint32_t x = 0; x < 20u; x++) {
-                if (R24_KSA_ASM) {
-                    const uint32_t dx = x ^ (x - 1u);
-                    if (x) {
-#pragma unroll
-                        for (int q = 0; q < NK; q++) kb[q] ^= dx;
-                    }
-                    rc4_ksa_asm_kb<NK>(sbase, sbase + (lane << 2), kb);
-                } else {
-                    const uint32_t xx = x * 0x01010101u;
-                    uint32_t kx[4] = {h[0] ^ xx, h[1] ^ xx, h[2] ^ xx, h[3] ^ xx};
-                    rc4_ksa<NK>(Sw, lane << 2, kx);
-                }
-                if (full) rc4_prga<16>(Sw, lane << 2, d);
-                else rc4_prga<2>(Sw, lane << 2, d);
-            }
-            if (full) {
-                ok = d[0] == p.u[0] && d[1] == p.u[1] && d[2] == p.u[2] && d[3] == p.u[3];
-            } else {
-                const bool pre = ((d[0] ^ p.u[0]) & 0xffffu) == 0u;
-                if (!__builtin_amdgcn_ballot_w64(valid && pre)) break;
-            }
-        }
-        if (valid && ok) report_hit(e, R_, e.start + g, cap, stop_on_first);
-    }
-}
-
-/* ================================================================== PDF R2..R4, owner password */
-/* ISO 32000-1 Algorithms 3 and 7 (include/dprf.h "owner password"): the owner key MD5((pw[:32] || PAD)[:32]) [50 more
- * MD5s over all 16 bytes] decrypts O into x, a padded user password, and x must pass the user check above as a
- * 32-byte candidate.  Two key derivations and two RC4 stages per candidate, on k_pdf_r24's workgroup shape. */
-
-/* The 32 padded password bytes of candidate g (pdf...c:136-137), LE words */
+/* The 32 padded password bytes of candidate g, pw[:32] || PAD[0:32-len] (pdf...c:136-137), LE words.  Reads the
+ * charset and PAD || PAD from the LDS overlay. */
 template <int MODE>
 DEVI void r24_padded_pw(const dprf_enum &e, const uint8_t *cs, const uint32_t *padw, const uint32_t padtail[8],
                         uint32_t g, uint32_t pw[8]) {
@@ -930,32 +718,8 @@ DEVI void r24_padded_pw(const dprf_enum &e, const uint8_t *cs, const uint32_t *p
         }
     }
 }
-/* Owner key (Algorithm 3 steps a-d): one MD5 block over the 32 padded bytes, then for R >= 3 fifty MD5s over the whole
- * 16-byte digest, whatever the key length (the user key's rounds hash h[0:n]) */
-template <int R>
-DEVI void r24_owner_key(const uint32_t pw[8], uint32_t h[4]) {
-    {
-        uint32_t m[16];
-#pragma unroll
-        for (int j = 0; j < 8; j++) { m[j] = pw[j]; m[8 + j] = 0u; }
-        m[8] = 0x80u;
-        m[14] = 256u;
-        md5_iv(h);
-        md5_compress(h, m);
-    }
-    if (R >= 3) {
-        for (int i = 0; i < 50; i++) {
-            uint32_t m[16];
-            m[0] = h[0]; m[1] = h[1]; m[2] = h[2]; m[3] = h[3]; m[4] = 0x80u;
-#pragma unroll
-            for (int j = 5; j < 16; j++) m[j] = 0u;
-            m[14] = 128u;
-            md5_iv(h);
-            md5_compress(h, m);
-        }
-    }
-}
-/* User key of the 32 password bytes x (r24_key's chain; x comes from the RC4 wave and may hold any byte) */
+/* User key of the 32 padded password bytes x: MD5(x || O || LE32(P) || ID [|| FFFFFFFF]) (pdf...c:136-139, :352-402),
+ * then 50 x MD5(h[0:n]) for R >= 3 (:150-155).  In an owner search x comes from the RC4 wave and may hold any byte. */
 template <int R, int NK>
 DEVI void r24_user_key(const dprf_pdf_params &p, const uint32_t x[8], uint32_t h[4]) {
     {
@@ -989,7 +753,181 @@ DEVI void r24_user_key(const dprf_pdf_params &p, const uint32_t x[8], uint32_t h
         }
     }
 }
+/* RC4 key of candidate g in a user-password search */
+template <int MODE, int R, int NK>
+DEVI void r24_key(const dprf_enum &e, const dprf_pdf_params &p, const uint8_t *cs, const uint32_t *padw,
+                  const uint32_t padtail[8], uint32_t g, uint32_t h[4]) {
+    uint32_t pw[8];
+    r24_padded_pw<MODE>(e, cs, padw, padtail, g, pw);
+    r24_user_key<R, NK>(p, pw, h);
+}
 
+/* One workgroup = one RC4 wave + one key wave, over NBAT batches of 64 candidates (round 2; rc4_wg.h).
+ *
+ * The RC4 wave owns the workgroup's 16 KiB S-box area (one 256-byte box per lane) and only ever runs KSAs and
+ * PRGAs; the key wave derives the RC4 keys (enumeration + MD5 of the padded password and document tail, and for
+ * R3/R4 the 50 MD5 iterations) of batch b+1 while the RC4 wave runs batch b.  Keys are handed over through the
+ * S-box area while it is free, between two barriers at each batch boundary; charset, PAD and the skip flag sit
+ * in an area of their own (16,720 B per workgroup: still 9 per CU).  The RC4 wave raises its issue priority
+ * (s_setprio 3), so the MD5s take only the VALU cycles the KSA chains leave free.
+ * Why: when one wave did both (round 1 - mid round 2), a wave hashing its keys held its S-box without running
+ * a KSA -- ~8 % of the CU's 9 KSA chains idle for R3/R4, ~15 % for R2.  Measured (tools/ab_libs.sh, MI355X):
+ * R3/R4 fused 464 M, split without / with the priority 458 / 481 M; a key wave that hashes nothing (probe) 484 M,
+ * so the MD5s are fully hidden; then the KSA group size re-tuned (rc4_ksa): R3/R4 513 M, R2 8.77 -> 9.79 G.
+ * Batches per workgroup, R3/R4: 2 / 4 / 8 = 472 / 480 / 481 M (G = 4), 6 / 8 / 12 = 513 / 513 / 507 M (G = 2);
+ * R2: 8 / 16 / 24 = 9.58 / 9.68 / 9.70 G.  Re-measured on the group-deferred KSA: R3/R4 6 / 8 / 12 batches
+ * 559 / 560 / 557 M, priority 0 / 1 / 3 529 / 560 / 560 M; R2 8 / 16 / 24 batches 11.08 / 11.25 / 11.32 G,
+ * priority 0 10.56 G.  Round 3 (asm KSA): 8 / 12 / 16 = 613 / 608 / 603 M; round 4, with consecutive launches on two
+ * streams (the last partial generation of one launch overlaps the next): 8 / 12 / 16 = 626.2 / 628.5 / 625.2 M (three
+ * alternating runs each, every run of 12 above the neighbouring 8), so 12.  R2 likewise: 16 / 24 / 36 / 48 = 12.23 /
+ * 12.27 / 12.32 / 12.31 G, so 36 (profiles/ab_r2_batches_r04l.txt). */
+#ifndef R34_BATCHES
+#define R34_BATCHES 12
+#endif
+#ifndef R2_BATCHES
+#define R2_BATCHES 36
+#endif
+#ifndef R24_PRIO
+#define R24_PRIO 3
+#endif
+/* 1: the KSA as the generated asm block (rc4_dev.h rc4_ksa_asm); 0: the C++ rc4_ksa (A/B builds) */
+#ifndef R24_KSA_ASM
+#define R24_KSA_ASM 1
+#endif
+/* dprf_results.pad_ bit of these kernels' LDS-address assumption (dprf_params.h) */
+#define R24_ERR_LDS 2u
+template <int NK>
+DEVI void r24_ksa(uint8_t *S, uint32_t sbase, uint32_t lane, const uint32_t k[4]) {
+    if (R24_KSA_ASM) rc4_ksa_asm<NK>(sbase, sbase + (lane << 2), k);
+    else rc4_ksa<NK>(S, lane << 2, k);
+}
+/* Whether the candidate with RC4 key h is a hit (`valid`: its index is inside the launch), by the RC4 wave of the user
+ * kernel; stage C(b) of k_pdf_r24_owner is a hand copy of this body (below: why), so a fix here is due there too.
+ * R2: RC4-40 over PAD, compare 32 bytes of U (:161-163, :184-189).  The first 4 keystream bytes decide for all but
+ * 2^-32 of the lanes: a wave continues the same keystream (i = 5.., j carried) only when one of its lanes matches
+ * U[0:4].
+ * R3/R4: c = RC4(key, MD5(PAD||ID)); c = RC4(key ^ x, c) for x = 1..19 (:167-174), compare 16 bytes.  Early reject:
+ * every pass first produces only 2 keystream bytes and the candidate survives iff c19[0:2] equals U[0:2]; a wave in
+ * which some lane survives (2^-16 per lane) redoes its candidates with the full keystream and the reference's
+ * complete 16-byte compare (:184-189). */
+template <int R, int NK>
+DEVI bool r24_check(uint8_t *S, uint32_t sbase, uint32_t lane, const dprf_pdf_params &p, const uint32_t h[4],
+                    bool valid) {
+    bool ok = false;
+    if (R == 2) {
+        uint32_t d[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) d[j] = p.pad[j];
+        r24_ksa<5>(S, sbase, lane, h);
+        uint32_t jj = 0;
+        rc4_prga_span<1, 4>(S, lane << 2, d, jj);
+        if (__builtin_amdgcn_ballot_w64(valid && d[0] == p.u[0])) {
+            rc4_prga_span<5, 32>(S, lane << 2, d, jj);
+            ok = true;
+#pragma unroll
+            for (int j = 0; j < 8; j++) ok = ok && d[j] == p.u[j];
+        }
+    } else
+    for (uint32_t full = 0; full < 2u; full++) {
+        uint32_t d[4] = {p.h2[0], p.h2[1], p.h2[2], p.h2[3]};
+        /* the asm KSA's key registers, made once per candidate; pass x's key (key ^ x) by XORing x ^ (x - 1)
+         * into their byte 0 (16 v_xor per pass, the same count as forming kx and extracting its bytes) */
+        uint32_t kb[NK];
+        rc4_kb_init<NK>(h, kb);
+        for (uint32_t x = 0; x < 20u; x++) {
+            if (R24_KSA_ASM) {
+                const uint32_t dx = x ^ (x - 1u);
+                if (x) {
+#pragma unroll
+                    for (int q = 0; q < NK; q++) kb[q] ^= dx;
+                }
+                rc4_ksa_asm_kb<NK>(sbase, sbase + (lane << 2), kb);
+            } else {
+                const uint32_t xx = x * 0x01010101u;
+                uint32_t kx[4] = {h[0] ^ xx, h[1] ^ xx, h[2] ^ xx, h[3] ^ xx};
+                rc4_ksa<NK>(S, lane << 2, kx);
+            }
+            if (full) rc4_prga<16>(S, lane << 2, d);
+            else rc4_prga<2>(S, lane << 2, d);
+        }
+        if (full) {
+            ok = d[0] == p.u[0] && d[1] == p.u[1] && d[2] == p.u[2] && d[3] == p.u[3];
+        } else {
+            const bool pre = ((d[0] ^ p.u[0]) & 0xffffu) == 0u;
+            if (!__builtin_amdgcn_ballot_w64(valid && pre)) break;
+        }
+    }
+    return valid && ok;
+}
+
+template <int R> struct r24_batches { static constexpr uint32_t v = R == 2 ? R2_BATCHES : R34_BATCHES; };
+/* The user kernel's LDS: the S-box area first (LDS address 0: rc4_wg_sbox_base), then the overlay the key wave reads
+ * -- 16,720 B per workgroup */
+struct r24_lds {
+    uint8_t S[RC4_WAVE_BYTES];
+    uint8_t cs[256];                                      /* charset */
+    uint32_t padw[16];                                    /* PAD || PAD */
+    uint32_t flag[4];                                     /* block_prologue's skip flag */
+};
+DEVI void r24_stage_pad(r24_lds &L, const dprf_pdf_params &p) {
+    if (threadIdx.x < 8) { L.padw[threadIdx.x] = p.pad[threadIdx.x]; L.padw[threadIdx.x + 8] = p.pad[threadIdx.x]; }
+}
+template <int MODE, int R, int NK>
+__global__ void __launch_bounds__(128, 5)   /* 18 waves per CU (9 workgroups): <= 102 VGPRs */
+k_pdf_r24(dprf_enum e, dprf_pdf_params p, dprf_results *R_, uint32_t cap, uint32_t stop_on_first) {
+    constexpr uint32_t NBAT = r24_batches<R>::v;
+    __shared__ __attribute__((aligned(16))) r24_lds L;
+    uint8_t *S = L.S;
+    r24_stage_pad(L, p);
+    /* per = candidates per thread of the 128-thread block: 64 * NBAT candidates */
+    if (!block_prologue<false>(e, nullptr, R_, stop_on_first, L.cs, nullptr, L.flag, NBAT / 2)) return;
+    uint32_t padtail[8];
+    r24_padtail<MODE>(e, p, padtail);
+    rc4_wg_run<NBAT, R24_PRIO>(
+        e, S, R24_KSA_ASM, R_, R24_ERR_LDS,
+        /* key wave: the RC4 key of candidate g */
+        [&](uint32_t g, uint32_t h[4]) { r24_key<MODE, R, NK>(e, p, L.cs, L.padw, padtail, g, h); },
+        /* RC4 wave: the verdict of batch b under the lane's key h */
+        [&](const rc4_wg &w, uint32_t sbase, uint32_t b, const uint32_t h[4]) {
+            const uint32_t g = w.base + 64u * b + rc4_wg_lane_id();
+            if (r24_check<R, NK>(S, sbase, w.lane, p, h, g < e.count))
+                report_hit(e, R_, e.start + g, cap, stop_on_first);
+        });
+}
+
+/* ================================================================== PDF R2..R4, owner password */
+/* ISO 32000-1 Algorithms 3 and 7 (include/dprf.h "owner password"): the owner key MD5((pw[:32] || PAD)[:32]) [50 more
+ * MD5s over all 16 bytes] decrypts O into x, a padded user password, and x must pass the user check above as a
+ * 32-byte candidate.  Two key derivations and two RC4 stages per candidate, on k_pdf_r24's workgroup shape.
+ * The kernel writes the workgroup frame, the PAD tail and the check stage out instead of using rc4_wg.h, r24_padtail
+ * and r24_check: built on them its 128-bit range instantiation measured 0.3 % below its rate in two sessions
+ * (HISTORY.md); r24_padded_pw and r24_user_key are the shared ones. */
+
+/* Owner key (Algorithm 3 steps a-d): one MD5 block over the 32 padded bytes, then for R >= 3 fifty MD5s over the whole
+ * 16-byte digest, whatever the key length (the user key's rounds hash h[0:n]) */
+template <int R>
+DEVI void r24_owner_key(const uint32_t pw[8], uint32_t h[4]) {
+    {
+        uint32_t m[16];
+#pragma unroll
+        for (int j = 0; j < 8; j++) { m[j] = pw[j]; m[8 + j] = 0u; }
+        m[8] = 0x80u;
+        m[14] = 256u;
+        md5_iv(h);
+        md5_compress(h, m);
+    }
+    if (R >= 3) {
+        for (int i = 0; i < 50; i++) {
+            uint32_t m[16];
+            m[0] = h[0]; m[1] = h[1]; m[2] = h[2]; m[3] = h[3]; m[4] = 0x80u;
+#pragma unroll
+            for (int j = 5; j < 16; j++) m[j] = 0u;
+            m[14] = 128u;
+            md5_iv(h);
+            md5_compress(h, m);
+        }
+    }
+}
 /* One workgroup = one RC4 wave + one key wave over NBAT batches of 64 candidates, as k_pdf_r24; per batch b
  *   O(b)  key wave: owner key of the batch's candidates
  *   D(b)  RC4 wave: x = O decrypted under it (R2: one RC4 pass; R3/R4: passes with key ^ 19 .. key ^ 0), 32 keystream
@@ -1351,20 +1289,21 @@ hipError_t launch_pdf_r5(const dprf_enum &e, const dprf_pdf_params &p, dprf_resu
 #undef L5
     return hipGetLastError();
 }
+/* R2-R4: the instantiation is (MODE, R, NK) of the user or of the owner kernel -- (R, NK) picked once, the mode once */
+template <int RR, int NK>
+static void launch_r24(const dprf_enum &e, const dprf_pdf_params &p, dprf_results *R, uint32_t cap, uint32_t stop,
+                       hipStream_t s) {
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, GRID(e.count, 64 * r24_batches<RR>::v), dim3(128), 0, s, e, p, R, cap, stop);
+    };
+    if (p.owner) go(e.mode == 0 ? k_pdf_r24_owner<0, RR, NK> : k_pdf_r24_owner<1, RR, NK>);
+    else go(e.mode == 0 ? k_pdf_r24<0, RR, NK> : k_pdf_r24<1, RR, NK>);
+}
 hipError_t launch_pdf_r24(const dprf_enum &e, const dprf_pdf_params &p, dprf_results *R, uint32_t cap,
                           uint32_t stop, hipStream_t s) {
-#define L24(M, RR, NK) hipLaunchKernelGGL((k_pdf_r24<M, RR, NK>), GRID(e.count, 64 * r24_batches<RR>::v), dim3(128), 0, s, e, p, R, cap, stop)
-#define L24O(M, RR, NK) hipLaunchKernelGGL((k_pdf_r24_owner<M, RR, NK>), GRID(e.count, 64 * r24_batches<RR>::v), dim3(128), 0, s, e, p, R, cap, stop)
-    if (p.owner) {
-        if (p.R == 2) { if (e.mode == 0) L24O(0, 2, 5); else L24O(1, 2, 5); }
-        else if (p.n == 16) { if (e.mode == 0) L24O(0, 3, 16); else L24O(1, 3, 16); }
-        else { if (e.mode == 0) L24O(0, 3, 5); else L24O(1, 3, 5); }
-    } else
-    if (p.R == 2) { if (e.mode == 0) L24(0, 2, 5); else L24(1, 2, 5); }
-    else if (p.n == 16) { if (e.mode == 0) L24(0, 3, 16); else L24(1, 3, 16); }
-    else { if (e.mode == 0) L24(0, 3, 5); else L24(1, 3, 5); }
-#undef L24O
-#undef L24
+    if (p.R == 2) launch_r24<2, 5>(e, p, R, cap, stop, s);
+    else if (p.n == 16) launch_r24<3, 16>(e, p, R, cap, stop, s);
+    else launch_r24<3, 5>(e, p, R, cap, stop, s);
     return hipGetLastError();
 }
 #endif /* DPRF_PART_PDF */

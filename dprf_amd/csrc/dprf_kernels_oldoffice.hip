@@ -11,7 +11,8 @@
  * reference verifier exists for this stream: the definition is pinned by tests/oldoffice_model.py and the public
  * vectors in tests/golden/oldoffice_vectors.json.
  *
- * The workgroup is k_pdf_r24's (dprf_kernels.hip): one RC4 wave that owns a 16 KiB S-box area (rc4_dev.h, one 256-byte
+ * The workgroup is k_pdf_r24's (dprf_kernels.hip; written out here and not on rc4_wg.h's driver: on the driver both
+ * families measured below the parent's rate, HISTORY.md): one RC4 wave that owns a 16 KiB S-box area (rc4_dev.h, one 256-byte
  * box per lane) and one key wave that hashes the RC4 keys of batch b + 1 while the RC4 wave runs batch b; the keys
  * change hands through the S-box area between two barriers.  16,656 bytes of LDS per workgroup: 9 workgroups per CU.
  *
@@ -248,13 +249,10 @@ hipError_t launch_oldoffice(const dprf_enum &e, const dprf_oldoffice_params &p, 
                             uint32_t stop, hipStream_t s) {
     /* the host refuses candidates longer than a slot: no long-list mode */
     if (e.mode > 1u || (p.sha1 && p.key_bytes != 5u && p.key_bytes != 16u)) return hipErrorInvalidValue;
-    const dim3 grid((e.count + 64u * OLDOFFICE_BATCHES - 1u) / (64u * OLDOFFICE_BATCHES)), block(128);
-    if (p.sha1) {
-        if (e.mode == 0) hipLaunchKernelGGL((k_oldoffice<0, true>), grid, block, 0, s, e, p, R, cap, stop);
-        else hipLaunchKernelGGL((k_oldoffice<1, true>), grid, block, 0, s, e, p, R, cap, stop);
-    } else {
-        if (e.mode == 0) hipLaunchKernelGGL((k_oldoffice<0, false>), grid, block, 0, s, e, p, R, cap, stop);
-        else hipLaunchKernelGGL((k_oldoffice<1, false>), grid, block, 0, s, e, p, R, cap, stop);
-    }
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, GRID(e.count, 64u * OLDOFFICE_BATCHES), dim3(128), 0, s, e, p, R, cap, stop);
+    };
+    if (p.sha1) go(e.mode == 0 ? k_oldoffice<0, true> : k_oldoffice<1, true>);
+    else go(e.mode == 0 ? k_oldoffice<0, false> : k_oldoffice<1, false>);
     return hipGetLastError();
 }

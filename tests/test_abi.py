@@ -94,6 +94,39 @@ def test_candidate_source_is_defined_once():
             assert re.search(r'^#include "dprf_cand\.h"', src, re.M), f
 
 
+def test_r24_shared_definitions():
+    """What PDF R2-R4's two kernels share has one definition: the padded-password builder and the user-key chain
+    (r24_key is the two in a row; it used to restate both), the PAD tail and the verdict check as functions, and the
+    workgroup frame of the user kernel in rc4_wg.h, whose driver the user kernel runs on.  k_pdf_r24_owner and
+    k_oldoffice keep the frame -- and the owner kernel the check stage -- written out, because on the shared code
+    they measured slower (HISTORY.md): the copies that remain are counted here, so a further one shows."""
+    csrc = os.path.join(REPO, "dprf_amd", "csrc")
+    text = dict((f, open(os.path.join(csrc, f)).read()) for f in sorted(os.listdir(csrc))
+                if f.endswith((".hip", ".cpp", ".h")))
+    assert "rc4_wg.h" in text
+
+    def defined(pat):
+        return [(f, len(re.findall(pat, src, re.M))) for f, src in text.items() if re.search(pat, src, re.M)]
+    func = r"^(?:DEVI|__device__|static|inline)[^;(]*\b%s\s*\("
+    for name in ("r24_check", "r24_padded_pw", "r24_user_key", "r24_key", "r24_padtail"):
+        assert defined(func % name) == [("dprf_kernels.hip", 1)], name
+    for name in ("rc4_wg_geometry", "rc4_wg_put", "rc4_wg_get", "rc4_wg_sbox_base", "rc4_wg_lane_id", "rc4_wg_run"):
+        assert defined(func % name) == [("rc4_wg.h", 1)], name
+    kern = text["dprf_kernels.hip"]
+    # r24_key composes the two builders and holds no MD5 of its own
+    body = re.search(r"\bDEVI void r24_key\s*\([^{]*\{(.*?)\n\}", kern, re.S).group(1)
+    assert "r24_padded_pw<" in body and "r24_user_key<" in body and "md5_compress" not in body
+    # the user-key chain and the list-mode padding have no second copy: both kernels call the shared ones
+    assert len(re.findall(r"\br24_user_key\s*<", kern)) == 2 and len(re.findall(r"\br24_padded_pw\s*<", kern)) == 2
+    # the user kernel runs on the driver
+    assert re.search(r"\brc4_wg_run<", kern) and re.search(r'^#include "rc4_wg\.h"', kern, re.M)
+    # the remaining hand copies: the verdict stage (r24_check and the owner kernel's stage C) and the lane-id asm
+    # (rc4_wg.h, the owner kernel, k_oldoffice; dprf_kernels_r6.hip has a v_mbcnt of its own, for another purpose)
+    assert defined(r"\brc4_prga_span\s*<\s*1\s*,\s*4\s*>\s*\(") == [("dprf_kernels.hip", 2)]
+    assert [d for d in defined(r"v_mbcnt_lo_u32_b32") if d[0] != "dprf_kernels_r6.hip"] == \
+        [("dprf_kernels.hip", 1), ("dprf_kernels_oldoffice.hip", 1), ("rc4_wg.h", 1)]
+
+
 def test_family_table_is_the_one_place_that_knows_a_family():
     """What the host knows of a kernel family is one row of FAMILIES in dprf_doc.cpp: every family name is written once
     in the host sources, the per-family refusal sentences live in the document unit only, and that unit is free of

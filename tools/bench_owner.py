@@ -9,7 +9,11 @@ median rate of each mode with its spread, their ratio, the launches of a timed c
 predict (DESIGN.md "Owner password").  Writes profiles/owner_rates_<build>.json (or --out) and prints one JSON line
 per family.
 
+With --window mask the same keyspace is searched as a uniform mask spelled on the device (dprf_search_mask): the
+list-mode instantiations of the same kernels, user and owner.
+
 Usage (on a machine with the GPU): python tools/bench_owner.py [--families pdf_r34,pdf_r2,...] [--max-seconds S]
+                                                                [--window mask]
 """
 import argparse
 import contextlib
@@ -32,9 +36,14 @@ EXPECTED = {"pdf_r34": 0.47, "pdf_r3": 0.47, "pdf_r3_40": 0.47, "pdf_r2": 0.47, 
 MODES = ("owner", "user")
 
 
-def timed(ctx, charset, pwlen, n):
+def timed(ctx, charset, pwlen, n, window="range"):
+    """One timed call: a range window, or ("mask") the same keyspace as a device-spelled uniform mask, which the
+    list-mode instantiation of the kernel verifies."""
     t = time.perf_counter()
-    _, nhits, st = ctx.search_range(charset, pwlen, 0, n)      # returns after the last result copy
+    if window == "mask":
+        _, nhits, st = ctx.search_mask([charset] * pwlen, 0, n)
+    else:
+        _, nhits, st = ctx.search_range(charset, pwlen, 0, n)  # returns after the last result copy
     dt = time.perf_counter() - t
     assert nhits == 0 and st["candidates"] == n, (nhits, st, n)
     return dt, st["launches"]
@@ -48,11 +57,13 @@ def main():
                     help="stop growing the window once a call runs this long, whatever its launches (0: no cap)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--window", default="range", choices=["range", "mask"],
+                    help="the call that is timed: a range window, or the same keyspace as a uniform mask (list-mode kernels)")
     a = ap.parse_args()
     build = _lib.build_id()
     S = bench.streams()
     result = {"build": build, "min_launches": a.min_launches, "max_seconds": a.max_seconds, "rounds": a.rounds,
-              "families": {}}
+              "window": a.window, "families": {}}
     for name in a.families.split(","):
         stream_name, charset, pwlen = bench.WORKLOADS[name][:3]
         with contextlib.redirect_stdout(io.StringIO()):
@@ -63,14 +74,14 @@ def main():
             ctx.set_pdf_password("owner")
             n = 1 << 20
             while True:
-                dt, launches = timed(ctx, charset, pwlen, n)
+                dt, launches = timed(ctx, charset, pwlen, n, a.window)
                 if launches >= a.min_launches or n >= space or (a.max_seconds and dt >= a.max_seconds):
                     break
                 grow = 2.0 if not a.max_seconds else min(2.0, max(1.1, a.max_seconds / max(dt, 1e-3)))
                 n = min(space, int(n * grow))
             for mode in MODES:                                  # warm-up of both modes at the timed size
                 ctx.set_pdf_password(mode)
-                timed(ctx, charset, pwlen, n)
+                timed(ctx, charset, pwlen, n, a.window)
             rates = {m: [] for m in MODES}
             launches = {}
             kernels = {}
@@ -78,7 +89,7 @@ def main():
                 for mode in MODES:                              # alternating: drift of the machine hits both alike
                     ctx.set_pdf_password(mode)
                     kernels[mode] = ctx.kernel
-                    dt, launches[mode] = timed(ctx, charset, pwlen, n)
+                    dt, launches[mode] = timed(ctx, charset, pwlen, n, a.window)
                     rates[mode].append(n / dt)
         rec = {"family": name, "stream": stream_name, "pwlen": pwlen, "candidates": n, "launches": launches,
                "kernels": kernels, "expected_ratio": EXPECTED.get(name)}
