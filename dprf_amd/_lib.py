@@ -19,6 +19,7 @@ MAX_PW, MAX_PW_RANGE, MAX_PW_R6 = 131071, 32, 176
 MAX_MASK_SYMBOLS = 2048
 MAX_RULES, MAX_RULE_FNS, MAX_RULE_WORDS, MAX_SPELL = 1 << 20, 32, 1 << 22, 1 << 20
 PDF_USER, PDF_OWNER = 0, 1
+KEY40_SPACE = 1 << 40           # DPRF_KEY40_SPACE: the keys of a 40-bit document (dprf_search_key40)
 _PDF_PASSWORDS = {"user": PDF_USER, "owner": PDF_OWNER}
 
 EXPORTS = ["dprf_abi_version", "dprf_last_error", "dprf_device_count", "dprf_device_list", "dprf_ctx_create",
@@ -139,6 +140,13 @@ def lib():
                                            ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64, ctypes.c_uint64,
                                            ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
             L.dprf_spell_rules.restype = ctypes.c_int
+            # additive to ABI 9 and detected by looking the symbol up (include/dprf.h "40-bit key search"): a library
+            # without it still loads, and search_key40 says so
+            if hasattr(L, "dprf_search_key40"):
+                L.dprf_search_key40.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64,
+                                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Stats)]
+                L.dprf_search_key40.restype = ctypes.c_int
             if L.dprf_abi_version() != ABI_VERSION:
                 raise ImportError("libdprf.so ABI %d != %d" % (L.dprf_abi_version(), ABI_VERSION))
             _lib = L
@@ -329,6 +337,20 @@ class Context:
         dprf_search_mask).  Returns (sorted hit indices -- keyspace indices --, total hits, stats dict)."""
         start, count = _check_window(start, count)
         return self._call(lib().dprf_search_mask, self._symbols(positions) + (start, count), stop_on_first, cap, start)
+
+    def search_key40(self, start, count, stop_on_first=False, cap=1 << 16):
+        """Verify the 40-bit keys [start, start+count) of a PDF R2, R3/R4 Length-40 or Office 97-2003 type 0 / 1 / 3
+        document: key index i stands for the five bytes of i written big-endian (dprf_amd.key40; include/dprf.h
+        "40-bit key search").  Returns (sorted hit key indices (at most cap), total hits, stats dict).
+        DprfError(E_DOMAIN) for every other document, (E_INVALID) for a window that leaves [0, 2^40) -- checked here
+        first: ctypes would take an oversized int modulo 2^64 without a word."""
+        start, count = int(start), int(count)
+        if start < 0 or count < 0 or start + count > KEY40_SPACE:
+            raise DprfError(E_INVALID, "key window [%d, +%d) leaves the 40-bit key space [0, 2^40)" % (start, count))
+        export = getattr(lib(), "dprf_search_key40", None)
+        if export is None:
+            raise DprfError(E_INVALID, "this libdprf.so has no dprf_search_key40: rebuild it")
+        return self._call(export, (start, count), stop_on_first, cap)
 
     @staticmethod
     def _word_blob(words):

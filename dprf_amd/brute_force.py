@@ -30,6 +30,9 @@ candidates go to libdprf.so in batches, one candidate per GPU lane.  Differences
 * rule mode (an extension; ``rules``, ``--rules``): every word of a wordlist under every rule of one or two rule files
   (:mod:`dprf_amd.rules`: "c $1", "sa@ so0"), applied on the device -- :func:`init_rules_brute_force`; ``--stdout``
   prints the candidates instead of verifying them.
+* 40-bit key search (an extension; ``--key40``): for the documents that carry only 40 bits of RC4 key (PDF R2, R3/R4
+  with Length 40, Office 97-2003 types 0 / 1 / 3) the keys themselves are searched, all 2^40 of them or a window
+  (:mod:`dprf_amd.key40`) -- :func:`init_key40_brute_force`.  It reports the key, not a password.
 
 The reference's four worker processes on one queue (:70-73, :92-95) are inside libdprf.so: one context
 spans the devices, and every search call fans out over them (one worker thread + HIP stream per GPU on a
@@ -44,6 +47,7 @@ import time
 
 from . import _lib
 from . import hybrid
+from . import key40
 from . import mask as masks
 from . import rules as rulemod
 
@@ -150,15 +154,20 @@ class Checkpoint:
     and their number) keeps its mask under a name of its own beside them, so it loads no mask search's file, no mask
     search loads its file, and a changed wordlist is refused.  A rule search (rules: the SHA-256 of its encoded rules
     and their number) adds those to the hybrid key of the bare word, so a changed rule file is refused like a changed
-    wordlist and neither search loads the other's file."""
+    wordlist and neither search loads the other's file.  A 40-bit key search (key_window: its first and last key
+    index) records "search": "key40" and the window; its cursor is a key index and `found` the key's hex digits."""
 
     def __init__(self, path, input_data, charset=None, pwlen=None, mask=None, custom=(), target="user",
-                 wordlist=None, rules=None):
+                 wordlist=None, rules=None, key_window=None):
         import hashlib
         self.path = path
         self.target = target
         self.key = {"stream_sha256": hashlib.sha256("*".join(map(str, input_data)).encode()).hexdigest()}
-        if wordlist is not None:
+        if key_window is not None:
+            # a 40-bit key search: the cursor is a key index; the key names the search and its window, so neither a
+            # password search's file nor another window's loads
+            self.key.update(search="key40", window=[int(key_window[0]), int(key_window[1])])
+        elif wordlist is not None:
             self.key.update(hybrid_mask=mask, custom=[c or "" for c in custom], wordlist_sha256=wordlist[0],
                             words=int(wordlist[1]))
             if rules is not None:
@@ -350,12 +359,14 @@ def init_rangebased_brute_force(input_data, password_range, charset=LOWERCASE, d
                            lambda idx: _index_to_password(idx, charset, password_range)))
 
 
-def _rounds(ctx, cp, done, space, tried, t0, search, spell, owner=False):
+def _rounds(ctx, cp, done, space, tried, t0, search, spell, owner=False, kernel=None, report=None, note=None):
     """Rounds of consecutive indices from `done` to the keyspace's end or the first round with a hit: search(start, n)
-    -> (lowest hit index or None, stats), spell(index) -> password.  Saves the cursor and reports after every round."""
+    -> (lowest hit index or None, stats), spell(index) -> password.  Saves the cursor and reports after every round.
+    kernel: the family that sizes the rounds when it is not the context's own; note(done, rate): a further progress
+    line per round; report: what replaces :func:`_report` at the end."""
     found, rate = None, 0.0
     ndev = len(getattr(ctx, "devices", [0]))
-    kernel = getattr(ctx, "kernel", None)
+    kernel = kernel or getattr(ctx, "kernel", None)
     first = first_round(kernel, ndev)
     while done < space and found is None:
         n = next_round(rate, space - done, round_seconds(kernel, rate, ndev), first)
@@ -367,7 +378,9 @@ def _rounds(ctx, cp, done, space, tried, t0, search, spell, owner=False):
         done += n
         cp.save(done, found)
         progress(t0, tried, space - done if found is None else 0)
-    _report(found, tried, t0, owner)
+        if note is not None:
+            note(done, rate)
+    (report or _report)(found, tried, t0, owner)
     return (1, found) if found is not None else (0, DEFAULT_PASSWORD)
 
 
@@ -605,6 +618,63 @@ def print_rule_candidates(input_data, wordlist, rules, devices=None, out=None):
         ctx.close()
 
 
+def _time_left(seconds):
+    seconds = int(seconds)
+    if seconds >= 86400:
+        return "%d d %d h" % (seconds // 86400, seconds % 86400 // 3600)
+    if seconds >= 3600:
+        return "%d h %d min" % (seconds // 3600, seconds % 3600 // 60)
+    return "%d min %d s" % (seconds // 60, seconds % 60) if seconds >= 60 else "%d s" % seconds
+
+
+def init_key40_brute_force(input_data, window=None, devices=None, checkpoint=None):
+    """Search the 40-bit keys of a PDF R2, R3/R4 Length-40 or Office 97-2003 type 0 / 1 / 3 document
+    (:mod:`dprf_amd.key40`, include/dprf.h "40-bit key search"): every key of the space, or of `window` -- "FROM-TO" as
+    key40.parse_window takes it, or a (first, last) pair of key indices, both inclusive -- so that several machines can
+    split the space by hand.  Returns (found, key_hex): the lowest key index of the window that verifies as ten hex
+    digits, or (0, "default_password_allocation").  The same rounds as range mode, one ctx.search_key40 call each with
+    stop_on_first.  Any other document raises DprfError(E_DOMAIN) with the library's reason before a key is tried.
+    checkpoint: a resumable cursor file keyed by "key40", the stream and the window."""
+    lo, hi = key40.parse_window(window) if window is None or isinstance(window, str) else (int(window[0]), int(window[1]))
+    if not 0 <= lo <= hi < key40.SPACE:
+        raise ValueError("key window [%d, %d] leaves the 40-bit key space" % (lo, hi))
+    cp = Checkpoint(checkpoint, input_data, key_window=(lo, hi))
+    done, prior = cp.load()
+    if prior is not None:
+        print("Checkpoint: search already finished, key %s" % prior)
+        return 1, prior
+    ctx = _context(input_data, devices)
+    t0 = time.time()
+    try:
+        ctx.search_key40(lo, 0)          # the domain, before anything is printed or tried
+        if done > lo:
+            print("Checkpoint: resuming at key %s" % key40.key_hex(min(done, key40.SPACE - 1)))
+
+        def search(start, n):
+            hits, _, st = ctx.search_key40(start, n, stop_on_first=True, cap=1)
+            return (hits[0] if hits else None), st
+
+        def note(at, rate):
+            left = hi + 1 - at
+            print("Key space: %.6f %% of 2^40 searched in this window, %.6f %% of 2^40 left in it%s" % (
+                100.0 * (at - lo) / key40.SPACE, 100.0 * left / key40.SPACE,
+                " (about %s at %.3g keys/s)" % (_time_left(left / rate), rate) if rate > 0 and left else ""))
+
+        def report(found, n, t0_, owner):
+            dt = max(time.time() - t0_, 1e-9)
+            print("Tried %d keys in %.3f s (%.0f keys/sec)" % (n, dt, n / dt))
+            if found is not None:
+                print("Key found: " + found)
+                fam = key40.family(input_data)
+                if fam:
+                    print(key40.SENTENCES[fam])
+
+        return _rounds(ctx, cp, max(done, lo), hi + 1, 0, t0, search, key40.key_hex, kernel=ctx.kernel + "_key40",
+                       report=report, note=note)
+    finally:
+        ctx.close()
+
+
 def init_listbased_brute_force(input_data, passwords, devices=None, owner=False):
     """An explicit candidate list, e.g. a server payload (brute_force.py:82-104): one library call over all
     devices; the lowest list index that verifies wins."""
@@ -729,10 +799,25 @@ def main(argv=None):
     parser.add_argument("--owner", action="store_true",
                         help="search the PDF's owner password (the one that lifts print / copy / edit restrictions) "
                              "instead of its user password; document type 3 only")
+    parser.add_argument("--key40", nargs="?", const="", default=None, metavar="FROM-TO",
+                        help="search the document's 40-bit RC4 key instead of a password (PDF R2, R3/R4 with Length "
+                             "40, Office 97-2003 RC4 types 0 / 1 / 3): all 2^40 keys, or the keys FROM-TO, ten hex "
+                             "digits each and both inclusive (i.e., 0000000000-3fffffffff for the first quarter)")
     parser.add_argument("--devices", default=None, help="comma-separated GPU ordinals (default: all)")
     parser.add_argument("--checkpoint", default=None, help="resumable cursor file (written after every round)")
     args = parser.parse_args(argv)
     customs = [getattr(args, "custom" + k) for k in "1234"]
+    if args.key40 is not None:
+        for flag, given in (("-pr/--passwordrange", args.passwordrange is not None), ("--charset", args.charset is not None),
+                            ("--mask", args.mask is not None), ("--wordlist", args.wordlist is not None),
+                            ("--rules", args.rules is not None), ("--stdout", args.stdout), ("--owner", args.owner),
+                            ("-1 .. -4", any(c is not None for c in customs))):
+            if given:
+                parser.error("--key40 searches keys, not passwords: it cannot be combined with %s" % flag)
+        try:
+            window = key40.parse_window(args.key40)
+        except ValueError as ex:
+            parser.error("--key40: %s" % ex)
     if args.rules is not None:
         if args.wordlist is None:
             parser.error("--rules needs a --wordlist: rules are applied to its words")
@@ -760,6 +845,21 @@ def main(argv=None):
     if not stream:
         sys.exit(0)
     devices = [int(x) for x in args.devices.split(",")] if args.devices else None
+    if args.key40 is not None:
+        input_data = parse_verification_data(stream)
+        print("Initializing 40-bit key search.")
+        try:
+            found, key = init_key40_brute_force(input_data, window, devices=devices, checkpoint=args.checkpoint)
+        except _lib.DprfError as ex:
+            if ex.code != _lib.E_DOMAIN:
+                raise
+            print(str(ex))               # the library's reason why the document is not a 40-bit one
+            sys.exit(1)
+        except KeyboardInterrupt:
+            sys.exit(0)
+        if not found:
+            print("No key of the searched window verifies.")
+        return found, key
     if args.rules is not None and args.stdout:
         n = print_rule_candidates(parse_verification_data(stream), args.wordlist, args.rules, devices=devices)
         return 0, n

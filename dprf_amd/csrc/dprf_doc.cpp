@@ -213,34 +213,34 @@ static const uint32_t NO_CUT = ~0u;
 #define NO_LONG_AGILE "longer than 32 UTF-16 units: long Office Agile candidates are not supported yet"
 #define NO_LONG_OLDOFFICE "longer than 32 UTF-16 units: long Office 97-2003 candidates are not supported yet"
 /* One row per kernel_kind, in the enum's order (the static_assert below holds the build to it).  Columns: the kind,
- * its name and owner-mode name, chunk policy, the verifier's cut, key words handed from the KDF to the check, long-list
+ * its name, owner-mode name and key-search name, chunk policy, the verifier's cut, key words handed from the KDF to the check, long-list
  * prehash and whether it writes keys, the refusal without a long-list mode, streams per device. */
 constexpr family FAMILIES[K_COUNT] = {
     /* a never-matching context launches nothing */
-    {K_NONE, "none", nullptr, {1u << 24, 1u << 20, 1u << 24, 100.0, 1u << 20, 256}, NO_CUT, 0, 0, false, nullptr, 1},
-    {K_OFFICE, "office_std", nullptr, POLICY_OFFICE, NO_CUT, 8, DPRF_LONG_SHA1_SALT16, true, nullptr, 1},
-    {K_ODT, "odf_aes256", nullptr, POLICY_ODT, NO_CUT, 8, DPRF_LONG_SHA256, true, nullptr, 1},
+    {K_NONE, "none", nullptr, nullptr, {1u << 24, 1u << 20, 1u << 24, 100.0, 1u << 20, 256}, NO_CUT, 0, 0, false, nullptr, 1},
+    {K_OFFICE, "office_std", nullptr, nullptr, POLICY_OFFICE, NO_CUT, 8, DPRF_LONG_SHA1_SALT16, true, nullptr, 1},
+    {K_ODT, "odf_aes256", nullptr, nullptr, POLICY_ODT, NO_CUT, 8, DPRF_LONG_SHA256, true, nullptr, 1},
     /* R2-R4 truncate at 32 bytes: never long */
-    {K_PDF_R24, "pdf_r24", "pdf_r24_owner", POLICY_R24, 32, 0, 0, false, nullptr, DPRF_R24_STREAMS},
+    {K_PDF_R24, "pdf_r24", "pdf_r24_owner", "pdf_r24_key40", POLICY_R24, 32, 0, 0, false, nullptr, DPRF_R24_STREAMS},
     /* R5: the prehash is the whole check */
-    {K_PDF_R5, "pdf_r5", "pdf_r5_owner", {1u << 27, 1u << 22, 1u << 31, 100.0, 1u << 22, 2048}, 127, 0, DPRF_LONG_R5,
+    {K_PDF_R5, "pdf_r5", "pdf_r5_owner", nullptr, {1u << 27, 1u << 22, 1u << 31, 100.0, 1u << 22, 2048}, 127, 0, DPRF_LONG_R5,
      false, nullptr, 1},
-    {K_PDF_R6, "pdf_r6", "pdf_r6_owner",
+    {K_PDF_R6, "pdf_r6", "pdf_r6_owner", nullptr,
      {1u << 22, 1u << DPRF_R6_LO_LOG2, 1u << DPRF_R6_HI_LOG2, DPRF_R6_TARGET_MS, 1u << 20, 64}, NO_CUT, 0,
      DPRF_LONG_SHA256_SALT8, true, nullptr, 1},
     /* Agile: Office's target and granularity; init / lo / tail are one resident generation of k_agile_kdf at the
      * occupancy it builds with (256 CUs x 4 SIMDs x waves x 64 lanes: 2^19 at 8 waves per SIMD for SHA-1, 2^18 at
      * 4 for SHA-512).  It hands over two keys of up to 8 words. */
-    {K_AGILE_SHA1, "office_agile_sha1", nullptr, POLICY_OFFICE, NO_CUT, 16, 0, false, NO_LONG_AGILE, 1},
-    {K_AGILE_SHA512, "office_agile_sha512", nullptr,
+    {K_AGILE_SHA1, "office_agile_sha1", nullptr, nullptr, POLICY_OFFICE, NO_CUT, 16, 0, false, NO_LONG_AGILE, 1},
+    {K_AGILE_SHA512, "office_agile_sha512", nullptr, nullptr,
      {1u << 18, 1u << 18, 1u << DPRF_OFFICE_HI_LOG2, DPRF_OFFICE_TARGET_MS, 1u << 18, 256}, NO_CUT, 16, 0, false,
      NO_LONG_AGILE, 1},
     /* Office 97-2003 RC4 (types 0 / 1) and RC4 CryptoAPI (types 3 / 4): one kernel, fast hashes between R2 and R4 in
      * cost -- pdf_r24's row, on one stream */
-    {K_OLDOFFICE_MD5, "office_rc4_md5", nullptr, POLICY_R24, NO_CUT, 0, 0, false, NO_LONG_OLDOFFICE, 1},
-    {K_OLDOFFICE_SHA1, "office_rc4_sha1", nullptr, POLICY_R24, NO_CUT, 0, 0, false, NO_LONG_OLDOFFICE, 1},
+    {K_OLDOFFICE_MD5, "office_rc4_md5", nullptr, "office_rc4_md5_key40", POLICY_R24, NO_CUT, 0, 0, false, NO_LONG_OLDOFFICE, 1},
+    {K_OLDOFFICE_SHA1, "office_rc4_sha1", nullptr, "office_rc4_sha1_key40", POLICY_R24, NO_CUT, 0, 0, false, NO_LONG_OLDOFFICE, 1},
     /* ODF 1.0 / 1.1: half of ODF 1.2's KDF and a check of about the same time again -- its row */
-    {K_ODF_BF, "odf_bf_sha1", nullptr, POLICY_ODT, NO_CUT, 8, 0, false,
+    {K_ODF_BF, "odf_bf_sha1", nullptr, nullptr, POLICY_ODT, NO_CUT, 8, 0, false,
      "longer than 64 bytes: long ODF 1.0/1.1 candidates are not supported yet", DPRF_ODF_STREAMS},
 };
 constexpr bool rows_in_order(int k = 0) { return k == K_COUNT || (FAMILIES[k].kind == k && rows_in_order(k + 1)); }
@@ -544,6 +544,44 @@ int check_pdf_password(const dprf_doc *c, int which) {
                         c->pdf_o_len, c->pdf_u_len);
     }
     return DPRF_OK;
+}
+
+/* What dprf_search_key40 refuses (include/dprf.h "40-bit key search"): a window past 2^40, and every document whose
+ * RC4 key is not 40 bits long.  A never-matching context (kind none) passes: it answers "no hit" as in every search. */
+int check_key40(const dprf_doc *c, uint64_t start, uint64_t count) {
+    if (start > DPRF_KEY40_SPACE || count > DPRF_KEY40_SPACE - start)
+        return fail(DPRF_E_INVALID, "key window [%llu, +%llu) exceeds the 40-bit key space (2^40 keys)",
+                    (unsigned long long)start, (unsigned long long)count);
+    switch (c->kind) {
+        case K_NONE: return DPRF_OK;
+        case K_PDF_R24:
+            /* R2: the reference takes a 5-byte key whatever Length says (pdf...c:161-163) */
+            if (c->pdf.R == 2 || c->pdf.n == 5) return DPRF_OK;
+            return fail(DPRF_E_DOMAIN, "40-bit key search: pdf R%u with a %u-bit RC4 key (Length %u), not a 40-bit document",
+                        c->pdf.R, 8 * c->pdf.n, 8 * c->pdf.n);
+        case K_PDF_R5:
+        case K_PDF_R6:
+            return fail(DPRF_E_DOMAIN, "40-bit key search: pdf R%u is AES-256 under a SHA-2 password hash, not a 40-bit "
+                        "document", c->pdf.R);
+        case K_OLDOFFICE_MD5: return DPRF_OK;
+        case K_OLDOFFICE_SHA1:
+            if (c->oldoffice.key_bytes == 5) return DPRF_OK;
+            return fail(DPRF_E_DOMAIN, "40-bit key search: Office 97-2003 type 4 (RC4 CryptoAPI) has a 128-bit key, not a "
+                        "40-bit document");
+        case K_OFFICE:
+            return fail(DPRF_E_DOMAIN, "40-bit key search: Office 2007 is AES-128 under 50,000 SHA-1 rounds, not a 40-bit "
+                        "document");
+        case K_AGILE_SHA1:
+        case K_AGILE_SHA512:
+            return fail(DPRF_E_DOMAIN, "40-bit key search: Office 2010/2013 Agile Encryption is AES under a spun hash, not "
+                        "a 40-bit document");
+        case K_ODT:
+            return fail(DPRF_E_DOMAIN, "40-bit key search: ODF 1.2 is AES-256 under PBKDF2, not a 40-bit document");
+        case K_ODF_BF:
+            return fail(DPRF_E_DOMAIN, "40-bit key search: ODF 1.0/1.1 is Blowfish with a 128-bit PBKDF2 key, not a 40-bit "
+                        "document");
+        default: return fail(DPRF_E_DOMAIN, "40-bit key search: not a 40-bit document");
+    }
 }
 
 /* ------------------------------------------------------------------ range mode and the spelled windows */
@@ -901,7 +939,8 @@ extern "C" uint64_t dprf_plan_chunk(const char *kernel, double rate_per_ms, uint
     for (int k = K_NONE + 1; k < K_COUNT; k++) {
         const family &f = FAMILIES[k];
         const bool owner = f.owner_name && !strcmp(kernel, f.owner_name);
-        if (owner || !strcmp(kernel, f.name))
+        /* a key search plans with the password family's policy (dprf_doc.h key40_name) */
+        if (owner || !strcmp(kernel, f.name) || (f.key40_name && !strcmp(kernel, f.key40_name)))
             return plan_chunk((kernel_kind)k, owner, rate_per_ms, remaining, total, ndev, inflight);
     }
     return 0;

@@ -60,6 +60,7 @@ struct family {
     kernel_kind kind;        /* the row's own index: the build fails when a row is missing or out of place */
     const char *name;        /* dprf_ctx_kernel, dprf_plan_chunk */
     const char *owner_name;  /* the PDF kinds: the name while the owner password is searched, else null */
+    const char *key40_name;  /* the kinds with 40-bit documents: the name of their key search (dprf_search_key40), else null */
     chunk_policy policy;
     uint32_t trunc;          /* bytes at which the format's verifier cuts a candidate: 32, 127, ~0u for nowhere */
     uint32_t key_words;      /* words per candidate of the KDF -> check hand-off in HBM; 0: one kernel, no hand-off */
@@ -76,6 +77,9 @@ const char *kind_name(kernel_kind k, bool owner = false);
 chunk_policy policy(kernel_kind k, bool owner = false);
 uint64_t round_up(uint64_t v, uint64_t g);
 uint64_t plan_chunk(kernel_kind k, bool owner, double rate, uint64_t remaining, uint64_t total, int ndev, int inflight);
+/* The key search of a family (dprf_search_key40) plans with the password family's policy, owner = false: the measured
+ * rate sizes the later chunks.  Its name, or null when the family has no 40-bit documents. */
+inline const char *key40_name(kernel_kind k) { return fam(k).key40_name; }
 
 /* ------------------------------------------------------------------ the document */
 /* What a context knows without a device; dprf_ctx (dprf_host.cpp) has it as its base. */
@@ -102,6 +106,10 @@ struct dprf_doc {
  * field count, the tag's parser, and on success the long-list parameters.  Fills fmt, flags, kind and the params. */
 int parse_document(dprf_doc *d, const char *const *fields, int nfields);
 int check_pdf_password(const dprf_doc *d, int which);   /* DPRF_PDF_USER / DPRF_PDF_OWNER on this document */
+/* dprf_search_key40 on this document: the window (start + count <= 2^40, computed without wrapping: DPRF_E_INVALID),
+ * then the domain -- PDF R2, R3/R4 with a 5-byte key, Office 97-2003 types 0 / 1 / 3, or a never-matching context;
+ * every other document is DPRF_E_DOMAIN with a message that says why it is not a 40-bit one */
+int check_key40(const dprf_doc *d, uint64_t start, uint64_t count);
 
 const dprf_aes_tables &aes_tables();
 

@@ -53,8 +53,11 @@ DEVI void sha256_msg2(uint32_t m[32], uint32_t total, uint32_t out[8]) {
 /* The file is compiled four times (Makefile): the Office kernels (DPRF_PART_OFFICE), the ODF kernels
  * (DPRF_PART_ODT) and the PDF R2-R5 kernels (DPRF_PART_PDF), each object with the LLVM machine-scheduler
  * strategy that measured fastest for it AND leaves its kernels without scratch (resource_gate.py), and the long-list
- * prehash (DPRF_PART_LONG). */
-#if !defined(DPRF_PART_OFFICE) && !defined(DPRF_PART_ODT) && !defined(DPRF_PART_PDF) && !defined(DPRF_PART_LONG)
+ * prehash (DPRF_PART_LONG).  A fifth time for the 40-bit key search of PDF R2-R4 (DPRF_PART_KEY40, never part of the
+ * default set): the verdict stage of k_pdf_r24 below and k_key40_pdf at the end of the PDF kernels, in an object of
+ * its own, so that the four above keep their machine code. */
+#if !defined(DPRF_PART_OFFICE) && !defined(DPRF_PART_ODT) && !defined(DPRF_PART_PDF) && !defined(DPRF_PART_LONG) && \
+    !defined(DPRF_PART_KEY40)
 #define DPRF_PART_OFFICE
 #define DPRF_PART_ODT
 #define DPRF_PART_PDF
@@ -781,6 +784,9 @@ DEVI void r24_key(const dprf_enum &e, const dprf_pdf_params &p, const uint8_t *c
  * streams (the last partial generation of one launch overlaps the next): 8 / 12 / 16 = 626.2 / 628.5 / 625.2 M (three
  * alternating runs each, every run of 12 above the neighbouring 8), so 12.  R2 likewise: 16 / 24 / 36 / 48 = 12.23 /
  * 12.27 / 12.32 / 12.31 G, so 36 (profiles/ab_r2_batches_r04l.txt). */
+#endif /* DPRF_PART_PDF */
+/* The batch counts, the KSA and the verdict stage are the key search's too (DPRF_PART_KEY40) */
+#if defined(DPRF_PART_PDF) || defined(DPRF_PART_KEY40)
 #ifndef R34_BATCHES
 #define R34_BATCHES 12
 #endif
@@ -861,6 +867,8 @@ DEVI bool r24_check(uint8_t *S, uint32_t sbase, uint32_t lane, const dprf_pdf_pa
 }
 
 template <int R> struct r24_batches { static constexpr uint32_t v = R == 2 ? R2_BATCHES : R34_BATCHES; };
+#endif /* DPRF_PART_PDF || DPRF_PART_KEY40 */
+#ifdef DPRF_PART_PDF
 /* The user kernel's LDS: the S-box area first (LDS address 0: rc4_wg_sbox_base), then the overlay the key wave reads
  * -- 16,720 B per workgroup */
 struct r24_lds {
@@ -1307,3 +1315,42 @@ hipError_t launch_pdf_r24(const dprf_enum &e, const dprf_pdf_params &p, dprf_res
     return hipGetLastError();
 }
 #endif /* DPRF_PART_PDF */
+
+#ifdef DPRF_PART_KEY40
+/* ================================================================== PDF R2..R4, 40-bit key search */
+/* dprf_search_key40 (include/dprf.h "40-bit key search"): the candidate is the RC4 key itself.  Index i = e.start + g
+ * stands for the five bytes of i written big-endian, so nothing is hashed and the workgroup has no key wave: one RC4
+ * wave of 64 threads over NBAT batches of 64 keys (rc4_wg.h rc4_wg_run1), the lane's key words formed in registers and
+ * judged by r24_check<R, 5> as it stands -- R2: RC4(key, PAD) against U[0:32]; R3/R4 with Length 40: the 20-pass
+ * chain against U[0:16].  LDS: the 16 KiB S-box area first (LDS address 0: rc4_wg_sbox_base) and the skip flag, 16,400
+ * B per workgroup: 9 per CU, as k_pdf_r24 (a tenth chain loses). */
+template <int R>
+__global__ void __launch_bounds__(64, 3)   /* 9 one-wave workgroups per CU: at most 3 waves on a SIMD */
+k_key40_pdf(dprf_enum e, dprf_pdf_params p, dprf_results *R_, uint32_t cap, uint32_t stop_on_first) {
+    constexpr uint32_t NBAT = r24_batches<R>::v;
+    __shared__ __attribute__((aligned(16))) key40_lds L;
+    uint8_t *S = L.S;
+    /* per = keys per thread of the 64-thread block: 64 * NBAT keys; no charset to stage */
+    if (!block_prologue<false, true, false>(e, nullptr, R_, stop_on_first, nullptr, nullptr, L.flag, NBAT)) return;
+    rc4_wg_run1<NBAT>(e, S, R24_KSA_ASM, R_, R24_ERR_LDS,
+                      [&](const rc4_wg &w, uint32_t sbase, uint32_t b) {
+                          const uint32_t g = w.base + 64u * b + rc4_wg_lane_id();
+                          const uint64_t i = e.start + g;   /* 64-bit: a launch may cross index 2^32 */
+                          uint32_t k[4];
+                          rc4_wg_key40(i, k);
+                          if (r24_check<R, 5>(S, sbase, w.lane, p, k, g < e.count))
+                              report_hit(e, R_, i, cap, stop_on_first);
+                      });
+}
+
+hipError_t launch_key40_pdf(const dprf_enum &e, const dprf_pdf_params &p, dprf_results *R, uint32_t cap,
+                            uint32_t stop, hipStream_t s) {
+    /* the host refuses every other document (dprf_doc.cpp check_key40) */
+    if (e.mode != DPRF_ENUM_KEY40 || p.R < 2u || p.R > 4u || (p.R != 2u && p.n != 5u)) return hipErrorInvalidValue;
+    if (p.R == 2)
+        hipLaunchKernelGGL(k_key40_pdf<2>, GRID(e.count, 64 * r24_batches<2>::v), dim3(64), 0, s, e, p, R, cap, stop);
+    else
+        hipLaunchKernelGGL(k_key40_pdf<3>, GRID(e.count, 64 * r24_batches<3>::v), dim3(64), 0, s, e, p, R, cap, stop);
+    return hipGetLastError();
+}
+#endif /* DPRF_PART_KEY40 */

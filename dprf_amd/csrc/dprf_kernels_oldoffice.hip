@@ -25,7 +25,11 @@
 #include "dprf_hits.h"
 #include "dprf_cand.h"
 #include "rc4_dev.h"
+#include "rc4_wg.h"
 
+/* The file is compiled twice (Makefile): the password kernel k_oldoffice, and with DPRF_PART_KEY40 the 40-bit key
+ * search k_key40_oldoffice at the end of the file, in an object of its own; the two share the verdict stage. */
+#ifndef DPRF_PART_KEY40
 namespace {
 /* ------------------------------------------------------------------ RC4 key of one candidate */
 /* Types 0 / 1: nine MD5 compressions at most (the first message is one block up to 27 characters, two from 28). */
@@ -129,6 +133,7 @@ DEVI void oldoffice_key(const dprf_enum &e, const dprf_oldoffice_params &p, cons
     else key_md5(p, c, k);
 }
 }  // namespace
+#endif /* !DPRF_PART_KEY40 */
 
 /* Batches of 64 candidates per workgroup; even, since the 128-thread block counts OLDOFFICE_BATCHES / 2 candidates
  * per thread.  Measured on MI355X (tools/bench_oldoffice.py, two alternating passes, G cand/s, MD5 / SHA-1 family):
@@ -148,6 +153,51 @@ DEVI void oldoffice_key(const dprf_enum &e, const dprf_oldoffice_params &p, cons
 /* dprf_results.pad_ bit of this kernel's LDS-address assumption (1, 2, 4, 8 are taken: dprf_params.h) */
 #define OLDOFFICE_ERR_LDS 16u
 
+/* The verdict of one lane under its 16-byte RC4 key k, by the RC4 wave of the key search (k_key40_oldoffice): the KSA,
+ * one continuous keystream over encryptedVerifier || encryptedVerifierHash, then the hash of the verifier against all
+ * 16 / 20 bytes of the decrypted hash: no prefilter.  The stage has a twin: k_oldoffice below keeps it written out --
+ * built on this function its object no longer compared equal to the measured one -- so a fix here is due there too. */
+template <bool SHA1>
+DEVI bool oldoffice_verdict(uint8_t *S, uint32_t sbase, uint32_t lane, const dprf_oldoffice_params &p,
+                            const uint32_t k[4]) {
+    if (OLDOFFICE_KSA_ASM) rc4_ksa_asm<16>(sbase, sbase + (lane << 2), k);
+    else rc4_ksa<16>(S, lane << 2, k);
+    bool ok;
+    if (SHA1) {
+        uint32_t d[9];
+#pragma unroll
+        for (int j = 0; j < 4; j++) d[j] = p.ev[j];
+#pragma unroll
+        for (int j = 0; j < 5; j++) d[4 + j] = p.evh[j];
+        rc4_prga<36>(S, lane << 2, d);
+        uint32_t w[16] = {bswap32(d[0]), bswap32(d[1]), bswap32(d[2]), bswap32(d[3]), 0x80000000u, 0, 0, 0,
+                          0, 0, 0, 0, 0, 0, 0, 128u};
+        uint32_t s[5];
+        sha1_iv(s);
+        sha1_compress(s, w);
+        ok = true;
+#pragma unroll
+        for (int j = 0; j < 5; j++) ok = ok && s[j] == bswap32(d[4 + j]);
+    } else {
+        uint32_t d[8];
+#pragma unroll
+        for (int j = 0; j < 4; j++) { d[j] = p.ev[j]; d[4 + j] = p.evh[j]; }
+        rc4_prga<32>(S, lane << 2, d);
+        uint32_t m[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) m[j] = 0u;
+        m[0] = d[0]; m[1] = d[1]; m[2] = d[2]; m[3] = d[3];
+        m[4] = 0x80u;
+        m[14] = 128u;
+        uint32_t s[4];
+        md5_iv(s);
+        md5_compress(s, m);
+        ok = s[0] == d[4] && s[1] == d[5] && s[2] == d[6] && s[3] == d[7];
+    }
+    return ok;
+}
+
+#ifndef DPRF_PART_KEY40
 template <int MODE, bool SHA1>
 __global__ void __launch_bounds__(128, 5)   /* 18 waves per CU (9 workgroups): <= 102 VGPRs */
 k_oldoffice(dprf_enum e, dprf_oldoffice_params p, dprf_results *R_, uint32_t cap, uint32_t stop_on_first) {
@@ -256,3 +306,79 @@ hipError_t launch_oldoffice(const dprf_enum &e, const dprf_oldoffice_params &p, 
     else go(e.mode == 0 ? k_oldoffice<0, false> : k_oldoffice<1, false>);
     return hipGetLastError();
 }
+
+#else /* DPRF_PART_KEY40 */
+/* ------------------------------------------------------------------ 40-bit key search */
+/* dprf_search_key40 (include/dprf.h "40-bit key search"): the candidate is the 40 bits of key the document has.  Index
+ * i = e.start + g stands for five bytes b0..b4, i written big-endian (rc4_wg_key40):
+ *   k_key40_oldoffice<false, W>   types 0 / 1: the bytes are h[0:5] of the second MD5; k = MD5(b0..b4 || LE32(0)), then
+ *                                 k_oldoffice's verdict stage
+ *   k_key40_oldoffice<true, 1>    type 3: the RC4 key is b0..b4 || 11 x 00 -- nothing is hashed before the KSA
+ * W = 2: k_oldoffice's workgroup (rc4_wg.h rc4_wg_run), the key wave running the one MD5 compression of batch b + 1
+ * behind the RC4 wave's batch b.  W = 1: a 64-thread workgroup without a key wave (rc4_wg_run1); with KEY40_MD5_WAVES 1
+ * the MD5 family hashes in the RC4 wave itself (the A/B of DESIGN.md 4g).  LDS: the S-box area and the skip flag,
+ * 16,400 B per workgroup: 9 per CU either way. */
+#ifndef KEY40_MD5_WAVES
+#define KEY40_MD5_WAVES 2
+#endif
+/* The 16-byte RC4 key of key index i */
+template <bool SHA1>
+DEVI void key40_key(uint64_t i, uint32_t k[4]) {
+    uint32_t b[4];
+    rc4_wg_key40(i, b);
+    if (SHA1) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) k[q] = b[q];
+    } else {
+        /* k = MD5(b0..b4 || LE32(0)): 9 bytes, one compression; all 16 bytes of k are the RC4 key */
+        uint32_t m[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) m[j] = 0u;
+        m[0] = b[0];
+        m[1] = b[1];
+        m[2] = 0x8000u;
+        m[14] = 72u;
+        md5_iv(k);
+        md5_compress(k, m);
+    }
+}
+
+template <bool SHA1, int WAVES>
+__global__ void __launch_bounds__(64 * WAVES, WAVES == 2 ? 5 : 3)   /* 9 workgroups per CU */
+k_key40_oldoffice(dprf_enum e, dprf_oldoffice_params p, dprf_results *R_, uint32_t cap, uint32_t stop_on_first) {
+    constexpr uint32_t NBAT = OLDOFFICE_BATCHES;
+    __shared__ __attribute__((aligned(16))) key40_lds L;
+    uint8_t *S = L.S;
+    /* per = keys per thread of the block: 64 * NBAT keys; no charset to stage */
+    if (!block_prologue<false, true, false>(e, nullptr, R_, stop_on_first, nullptr, nullptr, L.flag, NBAT / WAVES)) return;
+    /* RC4 wave: the verdict of batch b under the lane's key k */
+    const auto stage = [&](const rc4_wg &w, uint32_t sbase, uint32_t b, const uint32_t k[4]) {
+        const bool ok = oldoffice_verdict<SHA1>(S, sbase, w.lane, p, k);
+        const uint32_t g = w.base + 64u * b + rc4_wg_lane_id();
+        if (g < e.count && ok) report_hit(e, R_, e.start + g, cap, stop_on_first);
+    };
+    if constexpr (WAVES == 2)
+        rc4_wg_run<NBAT, OLDOFFICE_PRIO>(e, S, OLDOFFICE_KSA_ASM, R_, OLDOFFICE_ERR_LDS,
+                                         [&](uint32_t g, uint32_t k[4]) { key40_key<SHA1>(e.start + g, k); }, stage);
+    else
+        rc4_wg_run1<NBAT>(e, S, OLDOFFICE_KSA_ASM, R_, OLDOFFICE_ERR_LDS,
+                          [&](const rc4_wg &w, uint32_t sbase, uint32_t b) {
+                              uint32_t k[4];
+                              key40_key<SHA1>(e.start + (w.base + 64u * b + rc4_wg_lane_id()), k);
+                              stage(w, sbase, b, k);
+                          });
+}
+
+hipError_t launch_key40_oldoffice(const dprf_enum &e, const dprf_oldoffice_params &p, dprf_results *R, uint32_t cap,
+                                  uint32_t stop, hipStream_t s) {
+    /* the host refuses type 4 (a 128-bit key): dprf_doc.cpp check_key40 */
+    if (e.mode != DPRF_ENUM_KEY40 || (p.sha1 && p.key_bytes != 5u)) return hipErrorInvalidValue;
+    const dim3 grid = GRID(e.count, 64u * OLDOFFICE_BATCHES);
+    if (p.sha1)
+        hipLaunchKernelGGL((k_key40_oldoffice<true, 1>), grid, dim3(64), 0, s, e, p, R, cap, stop);
+    else
+        hipLaunchKernelGGL((k_key40_oldoffice<false, KEY40_MD5_WAVES>), grid, dim3(64 * KEY40_MD5_WAVES), 0, s, e, p, R,
+                           cap, stop);
+    return hipGetLastError();
+}
+#endif /* DPRF_PART_KEY40 */

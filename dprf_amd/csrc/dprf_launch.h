@@ -27,6 +27,13 @@ hipError_t launch_pdf_r5(const dprf_enum &e, const dprf_pdf_params &p, dprf_resu
                          uint32_t stop, hipStream_t s);
 hipError_t launch_pdf_r24(const dprf_enum &e, const dprf_pdf_params &p, dprf_results *R, uint32_t cap,
                           uint32_t stop, hipStream_t s);
+/* 40-bit key search (e.mode DPRF_ENUM_KEY40; dprf_kernels.hip and dprf_kernels_oldoffice.hip built with
+ * DPRF_PART_KEY40): keys e.start .. e.start + e.count - 1 of a PDF R2 / R3-R4 Length-40 or an Office 97-2003 type
+ * 0 / 1 / 3 document; any other document is hipErrorInvalidValue */
+hipError_t launch_key40_pdf(const dprf_enum &e, const dprf_pdf_params &p, dprf_results *R, uint32_t cap,
+                            uint32_t stop, hipStream_t s);
+hipError_t launch_key40_oldoffice(const dprf_enum &e, const dprf_oldoffice_params &p, dprf_results *R, uint32_t cap,
+                                  uint32_t stop, hipStream_t s);
 /* long list (e.mode 2): the records' first-message hash into e.keys, or (DPRF_LONG_R5) the whole R5 check */
 hipError_t launch_long_prehash(const dprf_enum &e, const dprf_long_params &lp, dprf_results *R, uint32_t cap,
                                uint32_t stop, hipStream_t s);

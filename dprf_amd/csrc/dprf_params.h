@@ -16,10 +16,13 @@
  * start + g of the device candidate buffer.  Long-list mode (round 4): candidate g is record start + g of a packed
  * blob of candidates longer than a slot -- k_long_prehash hashes the record's first message (Office H0, the ODF
  * start key, PDF R5's whole hash, R6's K0) into `keys`, and the format's kernels continue from there. */
+#define DPRF_ENUM_KEY40 3           /* dprf_enum.mode: the candidate is the key (dprf_search_key40): key g of the launch
+                                       is the 40-bit index start + g, its five bytes big-endian; only start and count
+                                       are read */
 struct dprf_enum {
     uint64_t start;
     uint32_t count;
-    uint32_t mode;                  /* 0 range, 1 list, 2 long list */
+    uint32_t mode;                  /* 0 range, 1 list, 2 long list, 3 key (DPRF_ENUM_KEY40) */
     uint32_t pwlen;                 /* range: fixed length (bytes); list / long list: longest candidate of the launch */
     uint32_t cslen;
     uint32_t div_m;                 /* u32 division by cslen: q = (mulhi(n,m) + ((n-mulhi)>>1)) >> s */

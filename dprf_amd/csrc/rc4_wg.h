@@ -1,5 +1,5 @@
 /* rc4_wg.h -- the two-wave RC4 workgroup of k_pdf_r24 (dprf_kernels.hip), device side.  Requires rc4_dev.h,
- * dprf_params.h and dprf_hits.h.  k_pdf_r24_owner and k_oldoffice (dprf_kernels_oldoffice.hip) have the same frame
+ * dprf_params.h, dprf_hits.h and dev_crypto.h (bswap32).  k_pdf_r24_owner and k_oldoffice (dprf_kernels_oldoffice.hip) have the same frame
  * written out: built on this header each measured below its rate (HISTORY.md), so a change to the protocol here is due
  * in both of them too.
  *
@@ -104,5 +104,32 @@ DEVI void rc4_wg_run(const dprf_enum &e, uint8_t *S, bool ksa_asm, dprf_results 
         rc4_wg_get<4>(S, w.lane, k);
         stage(w, sbase, b, k);
     }
+}
+
+/* LDS of a key-search workgroup: the S-box area first (LDS address 0: rc4_wg_sbox_base), then block_prologue's skip
+ * flag -- 16,400 B, 9 workgroups per CU */
+struct key40_lds {
+    uint8_t S[RC4_WAVE_BYTES];
+    uint32_t flag[4];
+};
+/* 40-bit key search (include/dprf.h): key index i stands for its five bytes written big-endian, b0 = i >> 32 first.
+ * The LE key words of b0..b4, zero-extended to 16 bytes */
+DEVI void rc4_wg_key40(uint64_t i, uint32_t k[4]) {
+    k[0] = bswap32((uint32_t)(i >> 8));
+    k[1] = (uint32_t)i & 0xffu;
+    k[2] = 0u;
+    k[3] = 0u;
+}
+
+/* The frame without a key wave, for a 64-thread workgroup whose RC4 keys need no hashing (the 40-bit key search: the
+ * key is the candidate index): stage(w, sbase, b) on batch b, no barrier and no exchange.  The geometry is the same,
+ * so block_prologue counts NBAT candidates per thread of the 64-thread block. */
+template <uint32_t NBAT, class Stage>
+DEVI void rc4_wg_run1(const dprf_enum &e, uint8_t *S, bool ksa_asm, dprf_results *R, uint32_t err, Stage stage) {
+    const rc4_wg w = rc4_wg_geometry<NBAT>(e);
+    uint32_t sbase;
+    if (!rc4_wg_sbox_base(S, ksa_asm, R, w.lane, err, 0u, sbase)) return;
+#pragma unroll 1
+    for (uint32_t b = 0; b < w.nb; b++) stage(w, sbase, b);
 }
 #endif

@@ -41,6 +41,8 @@ SCRATCH_LIMIT = {
     "k_oldoffice": 0,         # Office 97-2003 RC4 / RC4 CryptoAPI (dprf_kernels_oldoffice.hip)
     "k_odf_bf_kdf": 0,        # ODF 1.0 / 1.1 Blowfish-CFB (dprf_kernels_odf.hip)
     "k_odf_bf_check": 0,
+    "k_key40_pdf": 0,         # 40-bit key search (dprf_search_key40): PDF R2-R4, Office 97-2003
+    "k_key40_oldoffice": 0,
 }
 
 

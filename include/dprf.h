@@ -218,8 +218,9 @@ int dprf_ctx_last_call_devices(const dprf_ctx *ctx, dprf_device_stats *out, int 
  * as for the 2007 stream (ASCII range charset, one valid UTF-8 character per symbol, empty or invalid UTF-8 list
  * candidate DPRF_E_DOMAIN), except that a list candidate of more than 32 UTF-16 units (the 64-byte slot) is
  * DPRF_E_PWLEN, reported per candidate by dprf_list_status: long Office 97-2003 candidates are not supported yet.
- * Not done: PowerPoint 97-2003 (.ppt), XOR obfuscation, list candidates over 32 UTF-16 units, the 40-bit key-space
- * attacks (hashcat modes 9710 / 9720 / 9810 / 9820), John's type 5, decrypting the document body. */
+ * Types 0, 1 and 3 carry 40 bits of RC4 key: dprf_search_key40 (below, "40-bit key search") searches the keys themselves.
+ * Not done: PowerPoint 97-2003 (.ppt), XOR obfuscation, list candidates over 32 UTF-16 units, a password for a known
+ * key (hashcat's collider-#2 modes 9720 / 9820), John's type 5, decrypting the document body. */
 
 /* ---- ODF 1.0 / 1.1: Blowfish in CFB mode, SHA-1 (OpenOffice.org, StarOffice, Apache OpenOffice, LibreOffice < 3.5
  * and its "ODF 1.0/1.1" setting) ----
@@ -460,6 +461,48 @@ int dprf_search_rules(dprf_ctx *ctx, const uint32_t *fns, const uint32_t *rule_o
                       dprf_stats *stats);
 int dprf_spell_rules(dprf_ctx *ctx, const uint32_t *fns, const uint32_t *rule_off, int64_t nrules, uint64_t start,
                      uint64_t count, uint8_t *slots, uint8_t *lens);
+
+/* ---- 40-bit key search: the candidate is the RC4 key itself ----
+ * Additive to ABI 9 (DPRF_ABI_VERSION stays 9): a caller detects it by looking the symbol dprf_search_key40 up.
+ * Four of the families protect the document with only 40 bits of RC4 key, however long the password is, so the keys
+ * form a smaller space than any serious password space and can be searched to the end: DPRF_KEY40_SPACE = 2^40 keys.
+ * A password mode can fail on a long or unusual password; a key search cannot, and it returns the key, which is what
+ * decrypts the document (hashcat modes 10410 / 9710 / 9810).  A password search of at least 2^40 candidates already
+ * yields a colliding password of such a document in expectation, but with no bound and no completeness, and it pays for
+ * hashing a key search does not need.
+ * A key index i lies in [0, 2^40) and stands for the five bytes b0..b4 of i written big-endian: b0 = i >> 32,
+ * b4 = i & 0xff, hex spelling "%010x" of i.  That is the order itertools.product(range(256), repeat=5) gives, as in range
+ * mode: the leftmost byte is the most significant.  A key may hold any byte, 00 included.  PAD is the 32-byte padding
+ * string of the PDF standard.  What the five bytes are, and when index i verifies:
+ *   PDF R2                            the 5-byte RC4 key (5 bytes of an MD5; the reference uses a 5-byte key whatever
+ *                                     Length says, pdf_password_verifier.c:161-163):
+ *                                       RC4(b0..b4, PAD) == U[0:32]                                     (:184-189)
+ *   PDF R3 / R4 with Length / 8 == 5  the same 5-byte key k:
+ *                                       c = RC4(k, MD5(PAD || ID)); c = RC4(k XOR x, c) for x = 1..19   (:164-176)
+ *                                       c[0:16] == U[0:16]
+ *   Office 97-2003 types 0 / 1        h[0:5] of the second MD5 of the password hash:
+ *                                       k = MD5(b0..b4 || 00 00 00 00)   (all 16 bytes are the RC4 key)
+ *                                       d = RC4(k, encryptedVerifier || encryptedVerifierHash)
+ *                                       MD5(d[0:16]) == d[16:32]
+ *   Office 97-2003 type 3             the five key bytes of RC4 CryptoAPI's 40-bit key:
+ *                                       key = b0..b4 || eleven 00 bytes   (a 16-byte RC4 key)
+ *                                       d = RC4(key, encryptedVerifier || encryptedVerifierHash)   (36 bytes)
+ *                                       SHA1(d[0:16]) == d[16:36]
+ * Every other document is refused with DPRF_E_DOMAIN and a message that names why it is not a 40-bit one: PDF R3 / R4
+ * with a 16-byte key, R5, R6, Office 97-2003 type 4, Office 2007, Agile, and both ODF streams.
+ * The user / owner selection of a PDF context has no effect: there is one file key, and it is checked against /U.
+ * hits[] holds key indices, absolute and ascending, as range mode reports; stop_on_first, multi-device chunks, the
+ * cross-device stop, stats and the per-device records behave as dprf_search_range's.  A DPRF_FLAG_NEVER_MATCHES context
+ * answers "no hit" without device work.  dprf_ctx_kernel keeps returning the password family; the key searches have
+ * names of their own that dprf_plan_chunk knows ("pdf_r24_key40", "office_rc4_md5_key40", "office_rc4_sha1_key40"),
+ * planned with the password family's policy.
+ * Errors (the context still serves after a refused call): DPRF_E_INVALID -- a null argument, or start + count above
+ * 2^40 (computed without wrapping); DPRF_E_DOMAIN -- the context is not one of the four families above.
+ * Not done: a password for a known key (hashcat's collider-#2 modes 9720 / 9820), decrypting the document with the
+ * key, key lengths other than 40 bits. */
+#define DPRF_KEY40_SPACE (1ull << 40)
+int dprf_search_key40(dprf_ctx *ctx, uint64_t start, uint64_t count, int stop_on_first, uint64_t *hits, int64_t cap,
+                      int64_t *nhits, dprf_stats *stats);
 
 #ifdef __cplusplus
 }
