@@ -28,6 +28,9 @@ EXPORTS = ["dprf_abi_version", "dprf_last_error", "dprf_device_count", "dprf_dev
            "dprf_plan_chunk", "dprf_ctx_last_call_devices", "dprf_search_symbols", "dprf_search_mask",
            "dprf_ctx_set_pdf_password", "dprf_ctx_pdf_password", "dprf_ctx_set_words", "dprf_ctx_words",
            "dprf_words_status", "dprf_search_hybrid", "dprf_search_rules", "dprf_spell_rules"]
+# additive to ABI 9: a caller looks these up, a library without them still loads (include/dprf.h "40-bit key search",
+# "password for a known key").  Apart from EXPORTS, which is the ABI 9 baseline that every library has.
+ADDITIVE_EXPORTS = ["dprf_search_key40", "dprf_ctx_set_key40", "dprf_ctx_key40"]
 
 
 class DprfError(RuntimeError):
@@ -147,6 +150,11 @@ def lib():
                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64,
                                                 ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Stats)]
                 L.dprf_search_key40.restype = ctypes.c_int
+            if hasattr(L, "dprf_ctx_set_key40"):
+                L.dprf_ctx_set_key40.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+                L.dprf_ctx_set_key40.restype = ctypes.c_int
+                L.dprf_ctx_key40.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+                L.dprf_ctx_key40.restype = ctypes.c_int
             if L.dprf_abi_version() != ABI_VERSION:
                 raise ImportError("libdprf.so ABI %d != %d" % (L.dprf_abi_version(), ABI_VERSION))
             _lib = L
@@ -196,6 +204,17 @@ def _check_window(start, count):
     return start, count
 
 
+def _key40_bytes(key):
+    """Five key bytes from bytes of length 5 or a str of ten hex digits; ValueError for anything else."""
+    if isinstance(key, str):
+        if len(key) != 10 or any(ch not in "0123456789abcdefABCDEF" for ch in key):
+            raise ValueError("a 40-bit key is ten hex digits, not %r" % (key,))
+        return bytes.fromhex(key)
+    if isinstance(key, (bytes, bytearray)) and len(key) == 5:
+        return bytes(key)
+    raise ValueError("a 40-bit key is bytes of length 5 or ten hex digits, not %r" % (key,))
+
+
 class Context:
     """One document on one or more GPUs: the compiled form of the verifier argv brute_force.py builds per
     candidate (brute_force.py:163-197).  ``fields``: what parse_verification_data returns -- tag "office" (2007
@@ -206,9 +225,12 @@ class Context:
     "_owner" families).  ``devices``: a list of HIP ordinals (the library runs one worker
     thread and one stream per entry and splits every call over them); ``device``: one ordinal, or
     ALL_DEVICES for every gfx950 device.  ``pdf_password``: "user" (default) or "owner" -- which of a PDF's two
-    passwords the searches verify (ABI 9, include/dprf.h dprf_ctx_set_pdf_password)."""
+    passwords the searches verify (ABI 9, include/dprf.h dprf_ctx_set_pdf_password).  ``key40``: a known 40-bit key
+    (five bytes, or ten hex digits) the searches verify against instead of the document check (set_key40)."""
 
-    def __init__(self, fields, device=0, devices=None, pdf_password="user"):
+    def __init__(self, fields, device=0, devices=None, pdf_password="user", key40=None):
+        if key40 is not None:
+            key40 = _key40_bytes(key40)
         fields = list(fields)
         arr = (ctypes.c_char_p * len(fields))(*[_to_bytes(f) for f in fields])
         h = ctypes.c_void_p()
@@ -224,12 +246,14 @@ class Context:
         n = lib().dprf_ctx_devices(h, out, 64)
         self.devices = list(out[:min(n, 64)])
         self.device = self.devices[0]
-        if pdf_password != "user":
-            try:
+        try:
+            if pdf_password != "user":
                 self.set_pdf_password(pdf_password)
-            except Exception:
-                self.close()
-                raise
+            if key40 is not None:
+                self.set_key40(key40)
+        except Exception:
+            self.close()
+            raise
 
     def set_pdf_password(self, which):
         """Select the password every later search / verify call on this context checks: "user" or "owner".  Raises
@@ -246,6 +270,30 @@ class Context:
         if rc < 0:
             _check(rc)
         return "owner" if rc == PDF_OWNER else "user"
+
+    def set_key40(self, key):
+        """Give the context a known 40-bit key -- bytes of length 5 or ten hex digits, in the order search_key40 reports
+        (dprf_amd.key40) -- or None to clear it.  While a key is set every search / verify call reports the candidates
+        whose key derivation yields it: passwords that open the document, not necessarily the original one
+        (include/dprf.h "password for a known key").  ValueError for anything else, before ctypes sees it;
+        DprfError(E_DOMAIN) for a document that is not a 40-bit one, (E_INVALID) for a PDF context in owner mode; the
+        selection is unchanged then."""
+        raw = None if key is None else _key40_bytes(key)
+        export = getattr(lib(), "dprf_ctx_set_key40", None)
+        if export is None:
+            raise DprfError(E_INVALID, "this libdprf.so has no dprf_ctx_set_key40: rebuild it")
+        _check(export(self._h, raw))
+
+    def key40(self):
+        """The five bytes of the key that is set, or None."""
+        export = getattr(lib(), "dprf_ctx_key40", None)
+        if export is None:
+            return None
+        buf = ctypes.create_string_buffer(5)
+        rc = export(self._h, buf)
+        if rc < 0:
+            _check(rc)
+        return buf.raw if rc == 1 else None
 
     def close(self):
         if getattr(self, "_h", None):

@@ -33,6 +33,9 @@ candidates go to libdprf.so in batches, one candidate per GPU lane.  Differences
 * 40-bit key search (an extension; ``--key40``): for the documents that carry only 40 bits of RC4 key (PDF R2, R3/R4
   with Length 40, Office 97-2003 types 0 / 1 / 3) the keys themselves are searched, all 2^40 of them or a window
   (:mod:`dprf_amd.key40`) -- :func:`init_key40_brute_force`.  It reports the key, not a password.
+* password for a known key (an extension; ``key=``, ``--key HEX``): every candidate source verifies against the five
+  key bytes a ``--key40`` run found instead of the document (include/dprf.h dprf_ctx_set_key40): hashing alone, and any
+  password it reports opens the document -- it need not be the original one.
 
 The reference's four worker processes on one queue (:70-73, :92-95) are inside libdprf.so: one context
 spans the devices, and every search call fans out over them (one worker thread + HIP stream per GPU on a
@@ -68,8 +71,13 @@ OFFICE_TAGS = ("office", "oldoffice")   # the streams of document type 1: their 
 
 
 def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, checkpoint=None, mask=None,
-         custom_charsets=(), owner=False, wordlist=None, rules=None):
+         custom_charsets=(), owner=False, wordlist=None, rules=None, key=None):
     # The common entry point (brute_force.py:39-57)
+    if key is not None:
+        # a known 40-bit key (--key): every candidate source verifies against it (key40.known_key spells it)
+        if owner:
+            raise ValueError('A password for a known key is a user password (--key cannot be combined with --owner).')
+        key = key40.known_key(key)
     if rules is not None:
         # rule mode: a wordlist and nothing else beside the rules
         if wordlist is None:
@@ -102,18 +110,18 @@ def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, che
     try:
         if rules is not None:
             return init_rules_brute_force(input_data, wordlist, rules, devices=devices, checkpoint=checkpoint,
-                                          owner=owner)
+                                          owner=owner, key=key)
         if wordlist is not None:
             return init_hybrid_brute_force(input_data, wordlist, mask, custom_charsets=custom_charsets,
-                                           devices=devices, checkpoint=checkpoint, owner=owner)
+                                           devices=devices, checkpoint=checkpoint, owner=owner, key=key)
         if mask is not None:
             return init_mask_brute_force(input_data, mask, custom_charsets=custom_charsets, devices=devices,
-                                         checkpoint=checkpoint, owner=owner)
+                                         checkpoint=checkpoint, owner=owner, key=key)
         if password_range and not passwords:
             return init_rangebased_brute_force(input_data, password_range, charset=charset, devices=devices,
-                                               checkpoint=checkpoint, owner=owner)
+                                               checkpoint=checkpoint, owner=owner, key=key)
         if passwords and not password_range:
-            return init_listbased_brute_force(input_data, passwords, devices=devices, owner=owner)
+            return init_listbased_brute_force(input_data, passwords, devices=devices, owner=owner, key=key)
     except KeyboardInterrupt:
         sys.exit(0)
 
@@ -127,20 +135,35 @@ def _devices(devices):
     return list(devices)
 
 
-def _context(input_data, devices, owner=False):
+def _context(input_data, devices, owner=False, key=None):
     """One library context over the devices (the library splits every call over them).  owner: every call on it
     verifies the PDF's owner password -- the mode lives in the context, so each candidate source (range, symbols and
-    their host-spelled fallback, mask, list) checks the same password."""
+    their host-spelled fallback, mask, list) checks the same password.  key: five bytes of a known 40-bit key, and
+    every call verifies against it instead (Context.set_key40); the library refuses it together with owner."""
     if owner:
-        return _lib.Context(input_data, devices=_devices(devices), pdf_password="owner")
-    return _lib.Context(input_data, devices=_devices(devices))
+        return _lib.Context(input_data, devices=_devices(devices), pdf_password="owner", key40=key)
+    return _lib.Context(input_data, devices=_devices(devices), key40=key)
 
 
-def _report(found_pw, n, t0, owner=False):
+def _selected_context(input_data, devices, owner, key):
+    """_context for a search's selection; a plain user search calls it as it always did."""
+    if owner:
+        return _context(input_data, devices, owner=True)
+    return _context(input_data, devices, key=key) if key is not None else _context(input_data, devices)
+
+
+def _target(owner, key):
+    """What a checkpoint records of the check its search runs: "user", "owner", or the known key."""
+    return "key40:" + key.hex() if key is not None else "owner" if owner else "user"
+
+
+def _report(found_pw, n, t0, owner=False, key=None):
     dt = max(time.time() - t0, 1e-9)
     print("Tried %d candidates in %.3f s (%.0f H/sec)" % (n, dt, n / dt))
     if found_pw is not None:
         print("Correct password is '" + found_pw + "'" + (" (owner password)" if owner else ""))
+        if key is not None:
+            print(key40.COLLISION_NOTE % key.hex())
 
 
 class Checkpoint:
@@ -154,7 +177,8 @@ class Checkpoint:
     and their number) keeps its mask under a name of its own beside them, so it loads no mask search's file, no mask
     search loads its file, and a changed wordlist is refused.  A rule search (rules: the SHA-256 of its encoded rules
     and their number) adds those to the hybrid key of the bare word, so a changed rule file is refused like a changed
-    wordlist and neither search loads the other's file.  A 40-bit key search (key_window: its first and last key
+    wordlist and neither search loads the other's file.  A password search against a known key carries "target":
+    "key40:" and the key's ten hex digits, so it loads no other key's file and no document search's.  A 40-bit key search (key_window: its first and last key
     index) records "search": "key40" and the window; its cursor is a key index and `found` the key's hex digits."""
 
     def __init__(self, path, input_data, charset=None, pwlen=None, mask=None, custom=(), target="user",
@@ -307,7 +331,7 @@ def search_round(ctx, charset, pwlen, start, count, stop_on_first=True):
     return found, total
 
 
-def _resumable_search(input_data, cp, devices, owner, begin):
+def _resumable_search(input_data, cp, devices, owner, begin, key=None):
     """What range, mask and hybrid mode share: answer from a finished checkpoint without a context; else one context
     (closed at the end), "_dummy" first when the search starts at index 0 -- as the reference queues it beside the
     keyspace (brute_force.py:76) -- and the rounds from the checkpoint's cursor.  begin(ctx) does what the mode needs
@@ -317,7 +341,7 @@ def _resumable_search(input_data, cp, devices, owner, begin):
     if prior is not None:
         print("Checkpoint: search already finished, password '%s'" % prior)
         return 1, prior
-    ctx = _context(input_data, devices, owner=True) if owner else _context(input_data, devices)
+    ctx = _selected_context(input_data, devices, owner, key)
     t0 = time.time()
     tried = 0
     try:
@@ -327,11 +351,12 @@ def _resumable_search(input_data, cp, devices, owner, begin):
             tried += 1
             if hits:
                 cp.save(0, DUMMY)
-                _report(DUMMY, tried, t0, owner)
+                _report(DUMMY, tried, t0, owner, key)
                 return 1, DUMMY
         else:
             print("Checkpoint: resuming at index %d" % done)
-        return run(lambda start, space, search, spell: _rounds(ctx, cp, start, space, tried, t0, search, spell, owner),
+        return run(lambda start, space, search, spell: _rounds(ctx, cp, start, space, tried, t0, search, spell, owner,
+                                                               key=key),
                    done, t0)
     finally:
         ctx.close()
@@ -343,7 +368,7 @@ def _plain(space, search, spell):
 
 
 def init_rangebased_brute_force(input_data, password_range, charset=LOWERCASE, devices=None, checkpoint=None,
-                                owner=False):
+                                owner=False, key=None):
     """charset^password_range in product order, plus "_dummy" (brute_force.py:60-79, :199-219).
 
     Rounds of consecutive indices, each one library call over all devices with stop_on_first: a round
@@ -351,15 +376,16 @@ def init_rangebased_brute_force(input_data, password_range, charset=LOWERCASE, d
     round with a hit holds the lowest hit overall.  checkpoint: path of a resumable cursor file
     (:class:`Checkpoint`).  charset: see check_charset (raises before any device work)."""
     check_charset(charset)
-    cp = Checkpoint(checkpoint, input_data, charset, password_range, target="owner" if owner else "user")
+    cp = Checkpoint(checkpoint, input_data, charset, password_range, target=_target(owner, key))
     return _resumable_search(
         input_data, cp, devices, owner,
         lambda ctx: _plain(len(charset) ** password_range,
                            lambda start, n: search_round(ctx, charset, password_range, start, n),
-                           lambda idx: _index_to_password(idx, charset, password_range)))
+                           lambda idx: _index_to_password(idx, charset, password_range)), key=key)
 
 
-def _rounds(ctx, cp, done, space, tried, t0, search, spell, owner=False, kernel=None, report=None, note=None):
+def _rounds(ctx, cp, done, space, tried, t0, search, spell, owner=False, kernel=None, report=None, note=None,
+            key=None):
     """Rounds of consecutive indices from `done` to the keyspace's end or the first round with a hit: search(start, n)
     -> (lowest hit index or None, stats), spell(index) -> password.  Saves the cursor and reports after every round.
     kernel: the family that sizes the rounds when it is not the context's own; note(done, rate): a further progress
@@ -380,11 +406,15 @@ def _rounds(ctx, cp, done, space, tried, t0, search, spell, owner=False, kernel=
         progress(t0, tried, space - done if found is None else 0)
         if note is not None:
             note(done, rate)
-    (report or _report)(found, tried, t0, owner)
+    if report is not None:
+        report(found, tried, t0, owner)
+    else:
+        _report(found, tried, t0, owner, key)
     return (1, found) if found is not None else (0, DEFAULT_PASSWORD)
 
 
-def init_mask_brute_force(input_data, mask, custom_charsets=(), devices=None, checkpoint=None, owner=False):
+def init_mask_brute_force(input_data, mask, custom_charsets=(), devices=None, checkpoint=None, owner=False,
+                          key=None):
     """The candidates a mask spells (dprf_amd.mask), in product order, plus "_dummy" first as in range mode: the same
     rounds, one ctx.search_mask call each with stop_on_first, so the lowest keyspace index that verifies wins.  The
     candidates are spelled on the device; a mask whose candidates can exceed a list slot raises DprfError(E_PWLEN)
@@ -392,7 +422,7 @@ def init_mask_brute_force(input_data, mask, custom_charsets=(), devices=None, ch
     custom_charsets = tuple(custom_charsets or ())
     positions = masks.parse_mask(mask, custom_charsets)
     space = masks.space(positions)
-    cp = Checkpoint(checkpoint, input_data, mask=mask, custom=custom_charsets, target="owner" if owner else "user")
+    cp = Checkpoint(checkpoint, input_data, mask=mask, custom=custom_charsets, target=_target(owner, key))
 
     def begin(ctx):
         def search(start, n):
@@ -401,7 +431,7 @@ def init_mask_brute_force(input_data, mask, custom_charsets=(), devices=None, ch
 
         return _plain(space, search, lambda idx: masks.word(positions, idx))
 
-    return _resumable_search(input_data, cp, devices, owner, begin)
+    return _resumable_search(input_data, cp, devices, owner, begin, key=key)
 
 
 def wordlist_key(words):
@@ -427,7 +457,7 @@ def _slot_fit(kernel, fields, words, positions):
 
 
 def init_hybrid_brute_force(input_data, wordlist, mask="?w", custom_charsets=(), devices=None, checkpoint=None,
-                            owner=False):
+                            owner=False, key=None):
     """Every word of a wordlist with a mask around it (dprf_amd.hybrid: "?w?d?d", "?d?d?d?d-?w"), words in file
     order, per word the mask in product order, plus "_dummy" first as in range mode: the same rounds, one
     ctx.search_hybrid call each with stop_on_first, so the lowest keyspace index that verifies wins.  wordlist: a file
@@ -441,7 +471,7 @@ def init_hybrid_brute_force(input_data, wordlist, mask="?w", custom_charsets=(),
     custom_charsets = tuple(custom_charsets or ())
     positions, word_at = hybrid.parse_hybrid(mask, custom_charsets)
     words = hybrid.read_wordlist(wordlist) if isinstance(wordlist, str) else [hybrid._bytes(w) for w in wordlist]
-    cp = Checkpoint(checkpoint, input_data, mask=mask, custom=custom_charsets, target="owner" if owner else "user",
+    cp = Checkpoint(checkpoint, input_data, mask=mask, custom=custom_charsets, target=_target(owner, key),
                     wordlist=wordlist_key(words))
 
     def begin(ctx):
@@ -481,12 +511,12 @@ def init_hybrid_brute_force(input_data, wordlist, mask="?w", custom_charsets=(),
             hits, _, _ = ctx.verify_list(kept, stop_on_first=True, cap=1) if kept else ([], 0, None)
             found_pw = hybrid.text(kept[hits[0]]) if hits else None
             cp.save(space + len(late), found_pw)
-            _report(found_pw, len(kept), t0, owner)
+            _report(found_pw, len(kept), t0, owner, key)
             return (1, found_pw) if found_pw is not None else (0, DEFAULT_PASSWORD)
 
         return run
 
-    return _resumable_search(input_data, cp, devices, owner, begin)
+    return _resumable_search(input_data, cp, devices, owner, begin, key=key)
 
 
 def rules_key(rules):
@@ -554,7 +584,7 @@ def rule_text(candidate, office=False):
     return hybrid.text(candidate)
 
 
-def init_rules_brute_force(input_data, wordlist, rules, devices=None, checkpoint=None, owner=False):
+def init_rules_brute_force(input_data, wordlist, rules, devices=None, checkpoint=None, owner=False, key=None):
     """Every word of a wordlist under every rule (dprf_amd.rules), words in file order, per word the rules in file
     order, plus "_dummy" first as in range mode: the same rounds as hybrid mode, one ctx.search_rules call each with
     stop_on_first, so the lowest keyspace index that verifies wins.  wordlist: a file path, or a sequence of bytes
@@ -565,7 +595,7 @@ def init_rules_brute_force(input_data, wordlist, rules, devices=None, checkpoint
     rules = load_rules(rules)
     if not rules:
         raise ValueError("no rule of the rule language in the rule files")
-    cp = Checkpoint(checkpoint, input_data, mask="?w", custom=(), target="owner" if owner else "user",
+    cp = Checkpoint(checkpoint, input_data, mask="?w", custom=(), target=_target(owner, key),
                     wordlist=wordlist_key(words), rules=rules_key(rules))
 
     def begin(ctx):
@@ -584,7 +614,7 @@ def init_rules_brute_force(input_data, wordlist, rules, devices=None, checkpoint
 
         return run
 
-    return _resumable_search(input_data, cp, devices, owner, begin)
+    return _resumable_search(input_data, cp, devices, owner, begin, key=key)
 
 
 def print_rule_candidates(input_data, wordlist, rules, devices=None, out=None):
@@ -642,6 +672,7 @@ def init_key40_brute_force(input_data, window=None, devices=None, checkpoint=Non
     done, prior = cp.load()
     if prior is not None:
         print("Checkpoint: search already finished, key %s" % prior)
+        print(key40.KEY_HINT % prior)
         return 1, prior
     ctx = _context(input_data, devices)
     t0 = time.time()
@@ -668,6 +699,7 @@ def init_key40_brute_force(input_data, window=None, devices=None, checkpoint=Non
                 fam = key40.family(input_data)
                 if fam:
                     print(key40.SENTENCES[fam])
+                print(key40.KEY_HINT % found)
 
         return _rounds(ctx, cp, max(done, lo), hi + 1, 0, t0, search, key40.key_hex, kernel=ctx.kernel + "_key40",
                        report=report, note=note)
@@ -675,16 +707,16 @@ def init_key40_brute_force(input_data, window=None, devices=None, checkpoint=Non
         ctx.close()
 
 
-def init_listbased_brute_force(input_data, passwords, devices=None, owner=False):
+def init_listbased_brute_force(input_data, passwords, devices=None, owner=False, key=None):
     """An explicit candidate list, e.g. a server payload (brute_force.py:82-104): one library call over all
     devices; the lowest list index that verifies wins."""
     passwords = list(passwords)
-    ctx = _context(input_data, devices, owner=True) if owner else _context(input_data, devices)
+    ctx = _selected_context(input_data, devices, owner, key)
     t0 = time.time()
     try:
         hits, _, _ = ctx.verify_list(passwords, stop_on_first=True, cap=1)
         found = passwords[hits[0]] if hits else None
-        _report(found, len(passwords), t0, owner)
+        _report(found, len(passwords), t0, owner, key)
         return (1, found) if found is not None else (0, DEFAULT_PASSWORD)
     finally:
         ctx.close()
@@ -803,6 +835,10 @@ def main(argv=None):
                         help="search the document's 40-bit RC4 key instead of a password (PDF R2, R3/R4 with Length "
                              "40, Office 97-2003 RC4 types 0 / 1 / 3): all 2^40 keys, or the keys FROM-TO, ten hex "
                              "digits each and both inclusive (i.e., 0000000000-3fffffffff for the first quarter)")
+    parser.add_argument("--key", default=None, metavar="HEX",
+                        help="the document's 40-bit key is known (ten hex digits, as --key40 prints it): search a "
+                             "password with that key instead of the document's password, with -pr/--charset, --mask or "
+                             "--wordlist as usual; any such password opens the document")
     parser.add_argument("--devices", default=None, help="comma-separated GPU ordinals (default: all)")
     parser.add_argument("--checkpoint", default=None, help="resumable cursor file (written after every round)")
     args = parser.parse_args(argv)
@@ -811,13 +847,22 @@ def main(argv=None):
         for flag, given in (("-pr/--passwordrange", args.passwordrange is not None), ("--charset", args.charset is not None),
                             ("--mask", args.mask is not None), ("--wordlist", args.wordlist is not None),
                             ("--rules", args.rules is not None), ("--stdout", args.stdout), ("--owner", args.owner),
-                            ("-1 .. -4", any(c is not None for c in customs))):
+                            ("--key", args.key is not None), ("-1 .. -4", any(c is not None for c in customs))):
             if given:
                 parser.error("--key40 searches keys, not passwords: it cannot be combined with %s" % flag)
         try:
             window = key40.parse_window(args.key40)
         except ValueError as ex:
             parser.error("--key40: %s" % ex)
+    known = None
+    if args.key is not None:
+        for flag, given in (("--owner", args.owner), ("--key40", args.key40 is not None)):
+            if given:
+                parser.error("--key searches a user password with a known key: it cannot be combined with %s" % flag)
+        try:
+            known = key40.known_key(args.key)
+        except ValueError as ex:
+            parser.error("--key: %s" % ex)
     if args.rules is not None:
         if args.wordlist is None:
             parser.error("--rules needs a --wordlist: rules are applied to its words")
@@ -865,19 +910,19 @@ def main(argv=None):
         return 0, n
     if args.rules is not None:
         found, password = init(stream, None, None, devices=devices, checkpoint=args.checkpoint, owner=args.owner,
-                               wordlist=args.wordlist, rules=args.rules)
+                               wordlist=args.wordlist, rules=args.rules, key=known)
     elif args.wordlist is not None:
         found, password = init(stream, None, None, devices=devices, checkpoint=args.checkpoint, mask=args.mask,
-                               custom_charsets=customs, owner=args.owner, wordlist=args.wordlist)
+                               custom_charsets=customs, owner=args.owner, wordlist=args.wordlist, key=known)
     elif args.mask is not None:
         while customs and customs[-1] is None:
             customs.pop()
         found, password = init(stream, None, None, devices=devices, checkpoint=args.checkpoint, mask=args.mask,
-                               custom_charsets=customs, owner=args.owner)
+                               custom_charsets=customs, owner=args.owner, key=known)
     else:
         found, password = init(stream, args.passwordrange if args.passwordrange else 8, None,
                                charset=LOWERCASE if args.charset is None else args.charset, devices=devices,
-                               checkpoint=args.checkpoint, owner=args.owner)
+                               checkpoint=args.checkpoint, owner=args.owner, key=known)
     if not found:
         print("Password is not in brute-forced space.")
     return found, password

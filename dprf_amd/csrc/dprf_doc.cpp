@@ -213,51 +213,61 @@ static const uint32_t NO_CUT = ~0u;
 #define NO_LONG_AGILE "longer than 32 UTF-16 units: long Office Agile candidates are not supported yet"
 #define NO_LONG_OLDOFFICE "longer than 32 UTF-16 units: long Office 97-2003 candidates are not supported yet"
 /* One row per kernel_kind, in the enum's order (the static_assert below holds the build to it).  Columns: the kind,
- * its name, owner-mode name and key-search name, chunk policy, the verifier's cut, key words handed from the KDF to the check, long-list
- * prehash and whether it writes keys, the refusal without a long-list mode, streams per device. */
+ * its name, owner-mode name, key-search name and known-key (collider) name, chunk policy, the verifier's cut, key
+ * words handed from the KDF to the check, long-list prehash and whether it writes keys, the refusal without a
+ * long-list mode, streams per device. */
 constexpr family FAMILIES[K_COUNT] = {
     /* a never-matching context launches nothing */
-    {K_NONE, "none", nullptr, nullptr, {1u << 24, 1u << 20, 1u << 24, 100.0, 1u << 20, 256}, NO_CUT, 0, 0, false, nullptr, 1},
-    {K_OFFICE, "office_std", nullptr, nullptr, POLICY_OFFICE, NO_CUT, 8, DPRF_LONG_SHA1_SALT16, true, nullptr, 1},
-    {K_ODT, "odf_aes256", nullptr, nullptr, POLICY_ODT, NO_CUT, 8, DPRF_LONG_SHA256, true, nullptr, 1},
+    {K_NONE, "none", nullptr, nullptr, nullptr, {1u << 24, 1u << 20, 1u << 24, 100.0, 1u << 20, 256}, NO_CUT, 0, 0, false, nullptr, 1},
+    {K_OFFICE, "office_std", nullptr, nullptr, nullptr, POLICY_OFFICE, NO_CUT, 8, DPRF_LONG_SHA1_SALT16, true, nullptr, 1},
+    {K_ODT, "odf_aes256", nullptr, nullptr, nullptr, POLICY_ODT, NO_CUT, 8, DPRF_LONG_SHA256, true, nullptr, 1},
     /* R2-R4 truncate at 32 bytes: never long */
-    {K_PDF_R24, "pdf_r24", "pdf_r24_owner", "pdf_r24_key40", POLICY_R24, 32, 0, 0, false, nullptr, DPRF_R24_STREAMS},
+    {K_PDF_R24, "pdf_r24", "pdf_r24_owner", "pdf_r24_key40", "pdf_r24_collide", POLICY_R24, 32, 0, 0, false, nullptr,
+     DPRF_R24_STREAMS},
     /* R5: the prehash is the whole check */
-    {K_PDF_R5, "pdf_r5", "pdf_r5_owner", nullptr, {1u << 27, 1u << 22, 1u << 31, 100.0, 1u << 22, 2048}, 127, 0, DPRF_LONG_R5,
+    {K_PDF_R5, "pdf_r5", "pdf_r5_owner", nullptr, nullptr, {1u << 27, 1u << 22, 1u << 31, 100.0, 1u << 22, 2048}, 127, 0, DPRF_LONG_R5,
      false, nullptr, 1},
-    {K_PDF_R6, "pdf_r6", "pdf_r6_owner", nullptr,
+    {K_PDF_R6, "pdf_r6", "pdf_r6_owner", nullptr, nullptr,
      {1u << 22, 1u << DPRF_R6_LO_LOG2, 1u << DPRF_R6_HI_LOG2, DPRF_R6_TARGET_MS, 1u << 20, 64}, NO_CUT, 0,
      DPRF_LONG_SHA256_SALT8, true, nullptr, 1},
     /* Agile: Office's target and granularity; init / lo / tail are one resident generation of k_agile_kdf at the
      * occupancy it builds with (256 CUs x 4 SIMDs x waves x 64 lanes: 2^19 at 8 waves per SIMD for SHA-1, 2^18 at
      * 4 for SHA-512).  It hands over two keys of up to 8 words. */
-    {K_AGILE_SHA1, "office_agile_sha1", nullptr, nullptr, POLICY_OFFICE, NO_CUT, 16, 0, false, NO_LONG_AGILE, 1},
-    {K_AGILE_SHA512, "office_agile_sha512", nullptr, nullptr,
+    {K_AGILE_SHA1, "office_agile_sha1", nullptr, nullptr, nullptr, POLICY_OFFICE, NO_CUT, 16, 0, false, NO_LONG_AGILE, 1},
+    {K_AGILE_SHA512, "office_agile_sha512", nullptr, nullptr, nullptr,
      {1u << 18, 1u << 18, 1u << DPRF_OFFICE_HI_LOG2, DPRF_OFFICE_TARGET_MS, 1u << 18, 256}, NO_CUT, 16, 0, false,
      NO_LONG_AGILE, 1},
     /* Office 97-2003 RC4 (types 0 / 1) and RC4 CryptoAPI (types 3 / 4): one kernel, fast hashes between R2 and R4 in
      * cost -- pdf_r24's row, on one stream */
-    {K_OLDOFFICE_MD5, "office_rc4_md5", nullptr, "office_rc4_md5_key40", POLICY_R24, NO_CUT, 0, 0, false, NO_LONG_OLDOFFICE, 1},
-    {K_OLDOFFICE_SHA1, "office_rc4_sha1", nullptr, "office_rc4_sha1_key40", POLICY_R24, NO_CUT, 0, 0, false, NO_LONG_OLDOFFICE, 1},
+    {K_OLDOFFICE_MD5, "office_rc4_md5", nullptr, "office_rc4_md5_key40", "office_rc4_md5_collide",
+     POLICY_R24, NO_CUT, 0, 0, false, NO_LONG_OLDOFFICE, 1},
+    {K_OLDOFFICE_SHA1, "office_rc4_sha1", nullptr, "office_rc4_sha1_key40", "office_rc4_sha1_collide",
+     POLICY_R24, NO_CUT, 0, 0, false, NO_LONG_OLDOFFICE, 1},
     /* ODF 1.0 / 1.1: half of ODF 1.2's KDF and a check of about the same time again -- its row */
-    {K_ODF_BF, "odf_bf_sha1", nullptr, nullptr, POLICY_ODT, NO_CUT, 8, 0, false,
+    {K_ODF_BF, "odf_bf_sha1", nullptr, nullptr, nullptr, POLICY_ODT, NO_CUT, 8, 0, false,
      "longer than 64 bytes: long ODF 1.0/1.1 candidates are not supported yet", DPRF_ODF_STREAMS},
 };
 constexpr bool rows_in_order(int k = 0) { return k == K_COUNT || (FAMILIES[k].kind == k && rows_in_order(k + 1)); }
 static_assert(rows_in_order(), "FAMILIES needs one row per kernel_kind, in the enum's order");
 
-const char *kind_name(kernel_kind k, bool owner) {
+const char *kind_name(kernel_kind k, bool owner, bool collide) {
     const family &f = fam(k);
+    if (collide && f.collide_name) return f.collide_name;
     return owner && f.owner_name ? f.owner_name : f.name;
 }
-chunk_policy policy(kernel_kind k, bool owner) {
+chunk_policy policy(kernel_kind k, bool owner, bool collide) {
     chunk_policy p = fam(k).policy;
     if (owner && fam(k).owner_name) p.init = std::max(p.init / 2, p.lo);
+    /* a known key: hashing alone, 2 to 5 times the password family's rate (PDF R2 56 G cand/s, type 3
+     * 30 G), so the password family's ceiling of 2^30 would hold a launch at 19 to 36 ms of its own 100 ms target.
+     * 2^31 is the most a launch's 32-bit count and block offsets take (PDF R5's ceiling) */
+    if (collide && fam(k).collide_name) p.hi = std::max(p.hi, 1u << 31);
     return p;
 }
 uint64_t round_up(uint64_t v, uint64_t g) { return (v + g - 1) / g * g; }
-uint64_t plan_chunk(kernel_kind k, bool owner, double rate, uint64_t remaining, uint64_t total, int ndev, int inflight) {
-    const chunk_policy p = policy(k, owner);
+uint64_t plan_chunk(kernel_kind k, bool owner, double rate, uint64_t remaining, uint64_t total, int ndev, int inflight,
+                    bool collide) {
+    const chunk_policy p = policy(k, owner, collide);
     uint64_t want = p.init;
     if (rate > 0) {
         const double t = rate * p.target_ms;
@@ -536,6 +546,9 @@ int check_pdf_password(const dprf_doc *c, int which) {
     if (which != DPRF_PDF_USER && which != DPRF_PDF_OWNER)
         return fail(DPRF_E_INVALID, "dprf_ctx_set_pdf_password: unknown password kind %d", which);
     if (which == DPRF_PDF_OWNER) {
+        if (c->has_key40)
+            return fail(DPRF_E_INVALID, "dprf_ctx_set_pdf_password: a known key is set (dprf_ctx_set_key40), and a password "
+                        "for a known key is a user password (clear the key first)");
         /* what the owner check reads (include/dprf.h); a never-matching context (kind none) reads nothing */
         if (c->kind == K_PDF_R24 && c->pdf_o_len < 32)
             return fail(DPRF_E_DOMAIN, "pdf R%u owner check: O shorter than 32 bytes (%d)", c->pdf.R, c->pdf_o_len);
@@ -552,6 +565,10 @@ int check_key40(const dprf_doc *c, uint64_t start, uint64_t count) {
     if (start > DPRF_KEY40_SPACE || count > DPRF_KEY40_SPACE - start)
         return fail(DPRF_E_INVALID, "key window [%llu, +%llu) exceeds the 40-bit key space (2^40 keys)",
                     (unsigned long long)start, (unsigned long long)count);
+    return check_key40_domain(c);
+}
+/* The domain half: dprf_search_key40's, and dprf_ctx_set_key40's -- a known key is a key of the same documents */
+int check_key40_domain(const dprf_doc *c) {
     switch (c->kind) {
         case K_NONE: return DPRF_OK;
         case K_PDF_R24:
@@ -582,6 +599,16 @@ int check_key40(const dprf_doc *c, uint64_t start, uint64_t count) {
                         "document");
         default: return fail(DPRF_E_DOMAIN, "40-bit key search: not a 40-bit document");
     }
+}
+/* What dprf_ctx_set_key40 refuses (include/dprf.h "password for a known key"): a document that is not a 40-bit one,
+ * and a PDF in owner mode.  Clearing is never refused. */
+int check_set_key40(const dprf_doc *c, bool set) {
+    if (!set) return DPRF_OK;
+    if (const int rc = check_key40_domain(c)) return rc;
+    if (c->fmt == DPRF_FMT_PDF && c->pdf.owner)
+        return fail(DPRF_E_INVALID, "dprf_ctx_set_key40: the context searches the owner password; a password for a known "
+                    "key is a user password (select DPRF_PDF_USER first)");
+    return DPRF_OK;
 }
 
 /* ------------------------------------------------------------------ range mode and the spelled windows */
@@ -939,9 +966,10 @@ extern "C" uint64_t dprf_plan_chunk(const char *kernel, double rate_per_ms, uint
     for (int k = K_NONE + 1; k < K_COUNT; k++) {
         const family &f = FAMILIES[k];
         const bool owner = f.owner_name && !strcmp(kernel, f.owner_name);
+        const bool collide = f.collide_name && !strcmp(kernel, f.collide_name);
         /* a key search plans with the password family's policy (dprf_doc.h key40_name) */
-        if (owner || !strcmp(kernel, f.name) || (f.key40_name && !strcmp(kernel, f.key40_name)))
-            return plan_chunk((kernel_kind)k, owner, rate_per_ms, remaining, total, ndev, inflight);
+        if (owner || collide || !strcmp(kernel, f.name) || (f.key40_name && !strcmp(kernel, f.key40_name)))
+            return plan_chunk((kernel_kind)k, owner, rate_per_ms, remaining, total, ndev, inflight, collide);
     }
     return 0;
 }

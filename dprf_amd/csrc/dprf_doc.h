@@ -61,6 +61,7 @@ struct family {
     const char *name;        /* dprf_ctx_kernel, dprf_plan_chunk */
     const char *owner_name;  /* the PDF kinds: the name while the owner password is searched, else null */
     const char *key40_name;  /* the kinds with 40-bit documents: the name of their key search (dprf_search_key40), else null */
+    const char *collide_name; /* ... and the name while a known key is set (dprf_ctx_set_key40), else null */
     chunk_policy policy;
     uint32_t trunc;          /* bytes at which the format's verifier cuts a candidate: 32, 127, ~0u for nowhere */
     uint32_t key_words;      /* words per candidate of the KDF -> check hand-off in HBM; 0: one kernel, no hand-off */
@@ -71,12 +72,15 @@ struct family {
 };
 extern const family FAMILIES[K_COUNT];
 inline const family &fam(kernel_kind k) { return FAMILIES[k]; }
-const char *kind_name(kernel_kind k, bool owner = false);
+const char *kind_name(kernel_kind k, bool owner = false, bool collide = false);
 /* owner: the owner-password kernels of the PDF families do about twice the work per candidate: the user family's
- * policy with the first chunk halved (the measured rate sizes the later ones) */
-chunk_policy policy(kernel_kind k, bool owner = false);
+ * policy with the first chunk halved (the measured rate sizes the later ones).
+ * collide: a known key is set (dprf_ctx_set_key40) and the password searches run the collider kernels, hashing only:
+ * the password family's policy (dprf_doc.cpp policy() says what differs) */
+chunk_policy policy(kernel_kind k, bool owner = false, bool collide = false);
 uint64_t round_up(uint64_t v, uint64_t g);
-uint64_t plan_chunk(kernel_kind k, bool owner, double rate, uint64_t remaining, uint64_t total, int ndev, int inflight);
+uint64_t plan_chunk(kernel_kind k, bool owner, double rate, uint64_t remaining, uint64_t total, int ndev, int inflight,
+                    bool collide = false);
 /* The key search of a family (dprf_search_key40) plans with the password family's policy, owner = false: the measured
  * rate sizes the later chunks.  Its name, or null when the family has no 40-bit documents. */
 inline const char *key40_name(kernel_kind k) { return fam(k).key40_name; }
@@ -91,6 +95,8 @@ struct dprf_doc {
     dprf_oldoffice_params oldoffice{};/* Office 97-2003 RC4 (K_OLDOFFICE_*) */
     dprf_odt_params odt{};
     dprf_pdf_params pdf{};            /* .owner: which password the searches verify (dprf_ctx_set_pdf_password) */
+    bool has_key40 = false;           /* a known key is set (dprf_ctx_set_key40): the searches verify against it */
+    uint8_t key40[5] = {};            /* ... its five bytes, in the order dprf_search_key40 reports */
     int pdf_o_len = 0, pdf_u_len = 0; /* decoded /O and /U lengths: what the owner check needs is tested when it is selected */
     std::vector<uint32_t> odt_words;  /* first min(len,1024) ciphertext bytes, BE words */
     dprf_odf_params odf{};            /* ODF 1.0 / 1.1 Blowfish (K_ODF_BF) */
@@ -110,6 +116,16 @@ int check_pdf_password(const dprf_doc *d, int which);   /* DPRF_PDF_USER / DPRF_
  * then the domain -- PDF R2, R3/R4 with a 5-byte key, Office 97-2003 types 0 / 1 / 3, or a never-matching context;
  * every other document is DPRF_E_DOMAIN with a message that says why it is not a 40-bit one */
 int check_key40(const dprf_doc *d, uint64_t start, uint64_t count);
+/* The domain half alone: DPRF_OK on a 40-bit document or a never-matching context, else DPRF_E_DOMAIN and the sentence */
+int check_key40_domain(const dprf_doc *d);
+/* dprf_ctx_set_key40 on this document (set: a key is given, not cleared): the domain, then DPRF_E_INVALID for a PDF in
+ * owner mode -- a key collider finds the user password.  check_pdf_password refuses the other order. */
+int check_set_key40(const dprf_doc *d, bool set);
+/* The collider's compare words of the set key: LE words of its bytes 0..3 and byte 4, as MD5's h[0] and h[1] & 0xff */
+inline void key40_words(const dprf_doc *d, uint32_t k[2]) {
+    k[0] = (uint32_t)d->key40[0] | (uint32_t)d->key40[1] << 8 | (uint32_t)d->key40[2] << 16 | (uint32_t)d->key40[3] << 24;
+    k[1] = d->key40[4];
+}
 
 const dprf_aes_tables &aes_tables();
 

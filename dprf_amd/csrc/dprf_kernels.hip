@@ -55,9 +55,10 @@ DEVI void sha256_msg2(uint32_t m[32], uint32_t total, uint32_t out[8]) {
  * strategy that measured fastest for it AND leaves its kernels without scratch (resource_gate.py), and the long-list
  * prehash (DPRF_PART_LONG).  A fifth time for the 40-bit key search of PDF R2-R4 (DPRF_PART_KEY40, never part of the
  * default set): the verdict stage of k_pdf_r24 below and k_key40_pdf at the end of the PDF kernels, in an object of
- * its own, so that the four above keep their machine code. */
+ * its own, so that the four above keep their machine code.  A sixth time for the password search against a known
+ * 40-bit key (DPRF_PART_COLLIDE, likewise): the key derivation of k_pdf_r24's key wave and k_collide_pdf at the end. */
 #if !defined(DPRF_PART_OFFICE) && !defined(DPRF_PART_ODT) && !defined(DPRF_PART_PDF) && !defined(DPRF_PART_LONG) && \
-    !defined(DPRF_PART_KEY40)
+    !defined(DPRF_PART_KEY40) && !defined(DPRF_PART_COLLIDE)
 #define DPRF_PART_OFFICE
 #define DPRF_PART_ODT
 #define DPRF_PART_PDF
@@ -674,9 +675,12 @@ k_pdf_r5(dprf_enum e, dprf_pdf_params p, dprf_results *R, uint32_t cap, uint32_t
     }
 }
 
+#endif /* DPRF_PART_PDF */
 /* ================================================================== PDF R2..R4 (MD5 + RC4) */
 /* RC4 S-box layout, KSA and PRGA: rc4_dev.h; the two-wave workgroup and its driver: rc4_wg.h */
 
+/* The padded password, the user key and r24_key, the two in a row, are the collider's too (DPRF_PART_COLLIDE) */
+#if defined(DPRF_PART_PDF) || defined(DPRF_PART_COLLIDE)
 /* Range mode: pwlen <= 32 and a candidate's bytes past it are zero, so PAD at byte offset pwlen is launch-uniform:
  * eight words built once per key wave and OR-ed onto every candidate.  List mode reads PAD per lane: zeros here. */
 template <int MODE>
@@ -764,6 +768,8 @@ DEVI void r24_key(const dprf_enum &e, const dprf_pdf_params &p, const uint8_t *c
     r24_padded_pw<MODE>(e, cs, padw, padtail, g, pw);
     r24_user_key<R, NK>(p, pw, h);
 }
+#endif /* DPRF_PART_PDF || DPRF_PART_COLLIDE */
+#ifdef DPRF_PART_PDF
 
 /* One workgroup = one RC4 wave + one key wave, over NBAT batches of 64 candidates (round 2; rc4_wg.h).
  *
@@ -1354,3 +1360,57 @@ hipError_t launch_key40_pdf(const dprf_enum &e, const dprf_pdf_params &p, dprf_r
     return hipGetLastError();
 }
 #endif /* DPRF_PART_KEY40 */
+
+#ifdef DPRF_PART_COLLIDE
+/* ================================================================== PDF R2..R4, password for a known 40-bit key */
+/* dprf_ctx_set_key40 (include/dprf.h "password for a known key"): a candidate verifies when its user key -- the MD5 of
+ * the padded password and the document tail, for R3/R4 with Length 40 the 50 further MD5s of five bytes: r24_key, as
+ * k_pdf_r24's key wave computes it -- is the key the context was given.  Nothing of U is read and no RC4 runs: no S-box, no key wave, no two-wave frame.  The shape is
+ * k_pdf_r5's: a 256-thread block, PER candidates per thread 256 apart, 336 B of LDS (charset, PAD || PAD, skip flag).
+ * k0 / k1: the key's bytes 0..3 as an LE word and its byte 4 (dprf_doc.h key40_words) -- h[0] and h[1] & 0xff. */
+#ifndef COLLIDE_R2_PER
+#define COLLIDE_R2_PER 8            /* two compressions per candidate: the prologue is spread as for R5 */
+#endif
+#ifndef COLLIDE_R3_PER
+#define COLLIDE_R3_PER 2            /* 52 compressions per candidate: the prologue is noise either way */
+#endif
+struct collide_pdf_lds {
+    uint8_t cs[256];                                      /* charset */
+    uint32_t padw[16];                                    /* PAD || PAD */
+    uint32_t flag[4];                                     /* block_prologue's skip flag */
+};
+template <int MODE, int R>
+__global__ void __launch_bounds__(256, 4)
+k_collide_pdf(dprf_enum e, dprf_pdf_params p, uint32_t k0, uint32_t k1, dprf_results *R_, uint32_t cap,
+              uint32_t stop_on_first) {
+    constexpr uint32_t PER = R == 2 ? COLLIDE_R2_PER : COLLIDE_R3_PER;
+    __shared__ __attribute__((aligned(16))) collide_pdf_lds L;
+    if (threadIdx.x < 8) { L.padw[threadIdx.x] = p.pad[threadIdx.x]; L.padw[threadIdx.x + 8] = p.pad[threadIdx.x]; }
+    if (!block_prologue<false>(e, nullptr, R_, stop_on_first, L.cs, nullptr, L.flag, PER)) return;
+    uint32_t padtail[8];
+    r24_padtail<MODE>(e, p, padtail);
+    const uint32_t base = blockIdx.x * (256u * PER);
+#pragma unroll 1
+    for (uint32_t k = 0; k < PER; k++) {
+        if (base + 256u * k >= e.count) break;                       /* uniform */
+        const uint32_t g0 = base + 256u * k + threadIdx.x;
+        const bool valid = g0 < e.count;
+        const uint32_t g = valid ? g0 : e.count - 1u;
+        uint32_t h[4];
+        r24_key<MODE, R, 5>(e, p, L.cs, L.padw, padtail, g, h);
+        if (valid && h[0] == k0 && (h[1] & 0xffu) == k1) report_hit(e, R_, e.start + g, cap, stop_on_first);
+    }
+}
+
+hipError_t launch_collide_pdf(const dprf_enum &e, const dprf_pdf_params &p, const uint32_t key[2], dprf_results *R,
+                              uint32_t cap, uint32_t stop, hipStream_t s) {
+    /* the host refuses every other document and the owner mode (dprf_doc.cpp check_set_key40) */
+    if (e.mode > 1u || p.owner || p.R < 2u || p.R > 4u || (p.R != 2u && p.n != 5u)) return hipErrorInvalidValue;
+    const auto go = [&](auto kernel, uint32_t per) {
+        hipLaunchKernelGGL(kernel, GRID(e.count, 256u * per), dim3(256), 0, s, e, p, key[0], key[1], R, cap, stop);
+    };
+    if (p.R == 2) go(e.mode == 0 ? k_collide_pdf<0, 2> : k_collide_pdf<1, 2>, COLLIDE_R2_PER);
+    else go(e.mode == 0 ? k_collide_pdf<0, 3> : k_collide_pdf<1, 3>, COLLIDE_R3_PER);
+    return hipGetLastError();
+}
+#endif /* DPRF_PART_COLLIDE */

@@ -27,11 +27,15 @@
 #include "rc4_dev.h"
 #include "rc4_wg.h"
 
-/* The file is compiled twice (Makefile): the password kernel k_oldoffice, and with DPRF_PART_KEY40 the 40-bit key
- * search k_key40_oldoffice at the end of the file, in an object of its own; the two share the verdict stage. */
-#ifndef DPRF_PART_KEY40
+/* The file is compiled three times (Makefile): the password kernel k_oldoffice; with DPRF_PART_KEY40 the 40-bit key
+ * search k_key40_oldoffice, in an object of its own (the two share the verdict stage); and with DPRF_PART_COLLIDE the
+ * password search against a known key, k_collide_oldoffice at the end of the file, in an object of its own again. */
+#if !defined(DPRF_PART_KEY40) && !defined(DPRF_PART_COLLIDE)
 namespace {
 /* ------------------------------------------------------------------ RC4 key of one candidate */
+/* key_md5 and key_sha1 have twins that stop at the five key bytes, collide_md5 and collide_sha1 at the end of the file:
+ * with the two functions here split at that point and shared, k_oldoffice's object no longer compared equal to the
+ * measured one, so they stay as they are -- a fix here is due there too. */
 /* Types 0 / 1: nine MD5 compressions at most (the first message is one block up to 27 characters, two from 28). */
 DEVI void key_md5(const dprf_oldoffice_params &p, const cand &c, uint32_t k[4]) {
     uint32_t h[4];
@@ -133,7 +137,7 @@ DEVI void oldoffice_key(const dprf_enum &e, const dprf_oldoffice_params &p, cons
     else key_md5(p, c, k);
 }
 }  // namespace
-#endif /* !DPRF_PART_KEY40 */
+#endif /* !DPRF_PART_KEY40 && !DPRF_PART_COLLIDE */
 
 /* Batches of 64 candidates per workgroup; even, since the 128-thread block counts OLDOFFICE_BATCHES / 2 candidates
  * per thread.  Measured on MI355X (tools/bench_oldoffice.py, two alternating passes, G cand/s, MD5 / SHA-1 family):
@@ -197,7 +201,7 @@ DEVI bool oldoffice_verdict(uint8_t *S, uint32_t sbase, uint32_t lane, const dpr
     return ok;
 }
 
-#ifndef DPRF_PART_KEY40
+#if !defined(DPRF_PART_KEY40) && !defined(DPRF_PART_COLLIDE)
 template <int MODE, bool SHA1>
 __global__ void __launch_bounds__(128, 5)   /* 18 waves per CU (9 workgroups): <= 102 VGPRs */
 k_oldoffice(dprf_enum e, dprf_oldoffice_params p, dprf_results *R_, uint32_t cap, uint32_t stop_on_first) {
@@ -307,7 +311,7 @@ hipError_t launch_oldoffice(const dprf_enum &e, const dprf_oldoffice_params &p, 
     return hipGetLastError();
 }
 
-#else /* DPRF_PART_KEY40 */
+#elif defined(DPRF_PART_KEY40)
 /* ------------------------------------------------------------------ 40-bit key search */
 /* dprf_search_key40 (include/dprf.h "40-bit key search"): the candidate is the 40 bits of key the document has.  Index
  * i = e.start + g stands for five bytes b0..b4, i written big-endian (rc4_wg_key40):
@@ -381,4 +385,125 @@ hipError_t launch_key40_oldoffice(const dprf_enum &e, const dprf_oldoffice_param
                            cap, stop);
     return hipGetLastError();
 }
-#endif /* DPRF_PART_KEY40 */
+#else /* DPRF_PART_COLLIDE */
+/* ------------------------------------------------------------------ password for a known 40-bit key */
+/* dprf_ctx_set_key40 (include/dprf.h "password for a known key"): a candidate verifies when the 40 bits of key it
+ * derives are the key the context was given --
+ *   k_collide_oldoffice<MODE, false>   types 0 / 1: collide_md5, then h[0:5] == K; the third MD5 is not computed
+ *   k_collide_oldoffice<MODE, true>    type 3: collide_sha1, then s[0:5] == K
+ * Neither encryptedVerifier nor encryptedVerifierHash is read and no RC4 runs: no S-box, no key wave.  The shape is
+ * k_pdf_r5's: a 256-thread block, COLLIDE_OO_PER candidates per thread 256 apart, 272 B of LDS (charset, skip flag).
+ * k0 / k1: the key's bytes 0..3 as an LE word and its byte 4 (dprf_doc.h key40_words). */
+#ifndef COLLIDE_OO_PER
+#define COLLIDE_OO_PER 4
+#endif
+namespace {
+/* The first two stages of key_md5 (top of the file), its twin: k_oldoffice keeps key_md5 whole -- split and shared, its
+ * object no longer compared equal to the measured one -- so a fix there is due here too.  Eight MD5 compressions at
+ * most (the first message is one block up to 27 characters, two from 28). */
+DEVI void collide_md5(const dprf_oldoffice_params &p, const cand &c, uint32_t h[4]) {
+    {
+        /* h = MD5(pw16): the slot's words are the message as they stand (MD5 reads LE words) */
+        uint32_t b0[16], b1[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            b0[j] = (c.w[j] & le_keep_mask(j, c.len)) | le_pad80(j, c.len);
+            b1[j] = 0u;
+        }
+        /* a candidate that fills its whole slot has its terminator in the word after it */
+        b1[0] = c.len == 4u * DPRF_SLOT_WORDS ? 0x80u : 0u;
+        const bool two = c.len > 55u;
+        if (!two) b0[14] = c.len * 8u;       /* len <= 55: words 14, 15 hold no candidate byte */
+        b1[14] = c.len * 8u;
+        md5_iv(h);
+        md5_compress(h, b0);
+        if (two) md5_compress(h, b1);
+    }
+    /* h = MD5((h[0:5] || salt) x 16): 336 bytes, six blocks of p.rep with the five bytes OR-ed in: copy r of them
+     * starts at byte 21 r -- a compile-time word and shift */
+    const uint32_t lo = h[0], hi = h[1] & 0xffu;
+    md5_iv(h);
+#pragma unroll
+    for (int b = 0; b < 6; b++) {
+        uint32_t m[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) m[j] = p.rep[16 * b + j];
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int w = (21 * r) >> 2, s = 8 * ((21 * r) & 3);
+            const int j0 = w - 16 * b, j1 = w + 1 - 16 * b;
+            if (j0 >= 0 && j0 < 16) m[j0] |= lo << s;
+            if (j1 >= 0 && j1 < 16) m[j1] |= (s ? lo >> (32 - s) : 0u) | (hi << s);
+        }
+        md5_compress(h, m);
+    }
+}
+/* key_sha1 up to its second digest, its twin likewise: s = SHA1(SHA1(salt || pw16) || LE32(0)), two or three SHA-1
+ * compressions (salt || pw16 is one block up to 19 characters, two from 20) */
+DEVI void collide_sha1(const dprf_oldoffice_params &p, const cand &c, uint32_t s[5]) {
+    uint32_t h[5];
+    {
+        uint32_t m[32];
+        m[0] = p.salt[0]; m[1] = p.salt[1]; m[2] = p.salt[2]; m[3] = p.salt[3];
+        be_append<4>(m, c);
+        const uint32_t total = 16u + c.len, bits = total * 8u;
+        const bool two = total > 55u;
+        uint32_t b0[16], b1[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) { b0[j] = m[j]; b1[j] = m[16 + j]; }
+        if (!two) b0[15] = bits;
+        b1[15] = bits;
+        sha1_iv(h);
+        sha1_compress(h, b0);
+        if (two) sha1_compress(h, b1);
+    }
+    /* SHA1(h || LE32(0)): 24 bytes */
+    uint32_t w[16] = {h[0], h[1], h[2], h[3], h[4], 0u, 0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 192u};
+    sha1_iv(s);
+    sha1_compress(s, w);
+}
+}  // namespace
+template <int MODE, bool SHA1>
+__global__ void __launch_bounds__(256, 4)
+k_collide_oldoffice(dprf_enum e, dprf_oldoffice_params p, uint32_t k0, uint32_t k1, dprf_results *R_, uint32_t cap,
+                    uint32_t stop_on_first) {
+    constexpr uint32_t PER = COLLIDE_OO_PER;
+    __shared__ __attribute__((aligned(16))) uint32_t aux[64 + 4];
+    uint8_t *cs = (uint8_t *)aux;                         /* charset, 256 B */
+    if (!block_prologue<false>(e, nullptr, R_, stop_on_first, cs, nullptr, aux + 64, PER)) return;
+    const uint32_t base = blockIdx.x * (256u * PER);
+#pragma unroll 1
+    for (uint32_t k = 0; k < PER; k++) {
+        if (base + 256u * k >= e.count) break;                       /* uniform */
+        const uint32_t g0 = base + 256u * k + threadIdx.x;
+        const bool valid = g0 < e.count;
+        const uint32_t g = valid ? g0 : e.count - 1u;
+        cand c;
+        get_candidate<MODE, true>(e, cs, g, c);
+        bool ok;
+        if (SHA1) {
+            uint32_t s[5];
+            collide_sha1(p, c, s);
+            ok = bswap32(s[0]) == k0 && (bswap32(s[1]) & 0xffu) == k1;
+        } else {
+            uint32_t h[4];
+            collide_md5(p, c, h);
+            ok = h[0] == k0 && (h[1] & 0xffu) == k1;
+        }
+        if (valid && ok) report_hit(e, R_, e.start + g, cap, stop_on_first);
+    }
+}
+
+hipError_t launch_collide_oldoffice(const dprf_enum &e, const dprf_oldoffice_params &p, const uint32_t key[2],
+                                    dprf_results *R, uint32_t cap, uint32_t stop, hipStream_t s) {
+    /* the host refuses type 4 (a 128-bit key) and candidates longer than a slot (dprf_doc.cpp check_set_key40) */
+    if (e.mode > 1u || (p.sha1 && p.key_bytes != 5u)) return hipErrorInvalidValue;
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, GRID(e.count, 256u * COLLIDE_OO_PER), dim3(256), 0, s, e, p, key[0], key[1], R, cap,
+                           stop);
+    };
+    if (p.sha1) go(e.mode == 0 ? k_collide_oldoffice<0, true> : k_collide_oldoffice<1, true>);
+    else go(e.mode == 0 ? k_collide_oldoffice<0, false> : k_collide_oldoffice<1, false>);
+    return hipGetLastError();
+}
+#endif /* DPRF_PART_KEY40 / DPRF_PART_COLLIDE */

@@ -34,6 +34,13 @@ hipError_t launch_key40_pdf(const dprf_enum &e, const dprf_pdf_params &p, dprf_r
                             uint32_t stop, hipStream_t s);
 hipError_t launch_key40_oldoffice(const dprf_enum &e, const dprf_oldoffice_params &p, dprf_results *R, uint32_t cap,
                                   uint32_t stop, hipStream_t s);
+/* password for a known 40-bit key (dprf_ctx_set_key40; the same two sources built with DPRF_PART_COLLIDE): range or
+ * list candidates (e.mode 0 / 1) whose derived key is `key` -- the LE word of its bytes 0..3 and its byte 4 (dprf_doc.h
+ * key40_words).  The same documents as above, PDF in user mode; anything else is hipErrorInvalidValue */
+hipError_t launch_collide_pdf(const dprf_enum &e, const dprf_pdf_params &p, const uint32_t key[2], dprf_results *R,
+                              uint32_t cap, uint32_t stop, hipStream_t s);
+hipError_t launch_collide_oldoffice(const dprf_enum &e, const dprf_oldoffice_params &p, const uint32_t key[2],
+                                    dprf_results *R, uint32_t cap, uint32_t stop, hipStream_t s);
 /* long list (e.mode 2): the records' first-message hash into e.keys, or (DPRF_LONG_R5) the whole R5 check */
 hipError_t launch_long_prehash(const dprf_enum &e, const dprf_long_params &lp, dprf_results *R, uint32_t cap,
                                uint32_t stop, hipStream_t s);

@@ -43,6 +43,8 @@ SCRATCH_LIMIT = {
     "k_odf_bf_check": 0,
     "k_key40_pdf": 0,         # 40-bit key search (dprf_search_key40): PDF R2-R4, Office 97-2003
     "k_key40_oldoffice": 0,
+    "k_collide_pdf": 0,       # password for a known 40-bit key (dprf_ctx_set_key40): PDF R2-R4, Office 97-2003
+    "k_collide_oldoffice": 0,
 }
 
 

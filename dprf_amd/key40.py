@@ -45,6 +45,22 @@ def key_index(key):
     return int.from_bytes(key, "big")
 
 
+# After a key search's hit: how the key becomes a password (brute_force --key)
+KEY_HINT = ("To search a password with this key, run the password search with --key %s (and -pr, --mask or --wordlist): "
+            "any password it finds opens the document.")
+# After a hit of a password search against a known key
+COLLISION_NOTE = ("It is a password with the document's key %s: it opens the document, and it is not necessarily the "
+                  "password the document was saved with.")
+
+
+def known_key(key):
+    """The five bytes of a known key given as five bytes or as ten hex digits (--key, Context.set_key40); ValueError
+    for anything else."""
+    if not isinstance(key, (str, bytes, bytearray)):
+        raise ValueError("a 40-bit key is five bytes or ten hex digits (got %r)" % (key,))
+    return key_bytes(key_index(key))
+
+
 def parse_window(text):
     """"FROM-TO", ten hex digits each, both ends inclusive -> (first index, last index).  An empty string or None is
     the whole space."""

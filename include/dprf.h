@@ -218,9 +218,10 @@ int dprf_ctx_last_call_devices(const dprf_ctx *ctx, dprf_device_stats *out, int 
  * as for the 2007 stream (ASCII range charset, one valid UTF-8 character per symbol, empty or invalid UTF-8 list
  * candidate DPRF_E_DOMAIN), except that a list candidate of more than 32 UTF-16 units (the 64-byte slot) is
  * DPRF_E_PWLEN, reported per candidate by dprf_list_status: long Office 97-2003 candidates are not supported yet.
- * Types 0, 1 and 3 carry 40 bits of RC4 key: dprf_search_key40 (below, "40-bit key search") searches the keys themselves.
- * Not done: PowerPoint 97-2003 (.ppt), XOR obfuscation, list candidates over 32 UTF-16 units, a password for a known
- * key (hashcat's collider-#2 modes 9720 / 9820), John's type 5, decrypting the document body. */
+ * Types 0, 1 and 3 carry 40 bits of RC4 key: dprf_search_key40 (below, "40-bit key search") searches the keys themselves,
+ * and dprf_ctx_set_key40 ("password for a known key") turns a found key into a password.
+ * Not done: PowerPoint 97-2003 (.ppt), XOR obfuscation, list candidates over 32 UTF-16 units, John's type 5, decrypting
+ * the document body. */
 
 /* ---- ODF 1.0 / 1.1: Blowfish in CFB mode, SHA-1 (OpenOffice.org, StarOffice, Apache OpenOffice, LibreOffice < 3.5
  * and its "ODF 1.0/1.1" setting) ----
@@ -498,11 +499,44 @@ int dprf_spell_rules(dprf_ctx *ctx, const uint32_t *fns, const uint32_t *rule_of
  * planned with the password family's policy.
  * Errors (the context still serves after a refused call): DPRF_E_INVALID -- a null argument, or start + count above
  * 2^40 (computed without wrapping); DPRF_E_DOMAIN -- the context is not one of the four families above.
- * Not done: a password for a known key (hashcat's collider-#2 modes 9720 / 9820), decrypting the document with the
- * key, key lengths other than 40 bits. */
+ * Not done: decrypting the document with the key, key lengths other than 40 bits. */
 #define DPRF_KEY40_SPACE (1ull << 40)
 int dprf_search_key40(dprf_ctx *ctx, uint64_t start, uint64_t count, int stop_on_first, uint64_t *hits, int64_t cap,
                       int64_t *nhits, dprf_stats *stats);
+
+/* ---- password for a known key: the searches verify against five key bytes ----
+ * Additive to ABI 9 (DPRF_ABI_VERSION stays 9): a caller detects it by looking the symbol dprf_ctx_set_key40 up.
+ * dprf_search_key40 ends with a key, and a key cannot be typed into a viewer.  A context of one of the four 40-bit
+ * families can be given that key -- five bytes K = b0..b4 in the order dprf_search_key40 reports -- and from then on a
+ * candidate verifies exactly when its key derivation yields K (hashcat's collider-#2 modes 10420 / 9720 / 9820).  Any
+ * such password opens the document; it need not be the one the document was saved with.  Nothing of /U,
+ * encryptedVerifier or encryptedVerifierHash is read, and no RC4 runs: the check is the hashing alone.  PAD is the
+ * 32-byte padding string of the PDF standard, pw16 the candidate in UTF-16LE:
+ *   PDF R2                            h = MD5((pw[:32] || PAD)[:32] || O || LE32(P) || ID [|| FFFFFFFF if R >= 4 and
+ *                                     !EncryptMetadata]);  h[0:5] == K
+ *   PDF R3 / R4 with Length / 8 == 5  the same h, then 50 x h = MD5(h[0:5]);  h[0:5] == K
+ *   Office 97-2003 types 0 / 1        h = MD5(pw16); h = MD5((h[0:5] || salt) x 16);  h[0:5] == K  (the third MD5 of the
+ *                                     password check is not computed)
+ *   Office 97-2003 type 3             h = SHA1(salt || pw16); k = SHA1(h || 00 00 00 00);  k[0:5] == K
+ * Truncation and candidate lengths are those of the family's password search: PDF cuts at 32 bytes, Office takes at
+ * most 32 UTF-16 units in a slot and more is DPRF_E_PWLEN.
+ * While a key is set dprf_search_range, dprf_search_symbols, dprf_search_mask, dprf_verify_list, dprf_search_hybrid and
+ * dprf_search_rules verify against K, with hit indices, stop_on_first, multi-device chunks, the cross-device stop, stats,
+ * the per-device records and dprf_list_status as before.  Several candidates of one window may verify -- that is the
+ * purpose -- and all are reported, ascending.  key == NULL clears the key and restores the document check exactly.
+ * dprf_search_key40 and dprf_spell_rules are unaffected by the selection.  The setter takes the context's call mutex (it
+ * waits for a running call).  dprf_ctx_key40 returns 1 and writes the five bytes (key may be NULL) when a key is set,
+ * else 0.
+ * Errors (neither changes the selection, and the context still serves): DPRF_E_DOMAIN -- the document is not a 40-bit
+ * one, with dprf_search_key40's sentence; DPRF_E_INVALID -- a PDF context in owner mode: a key collider finds the user
+ * password.  dprf_ctx_set_pdf_password(ctx, DPRF_PDF_OWNER) while a key is set is DPRF_E_INVALID likewise.  A
+ * DPRF_FLAG_NEVER_MATCHES context accepts a key and finds nothing, without device work.
+ * While a key is set dprf_ctx_kernel returns "pdf_r24_collide", "office_rc4_md5_collide" or "office_rc4_sha1_collide",
+ * families dprf_plan_chunk knows (the password family's policy with a ceiling of 2^31 candidates per launch; the
+ * measured rate sizes the later chunks).
+ * Not done: a server / client protocol that carries the key, key lengths other than 40 bits. */
+int dprf_ctx_set_key40(dprf_ctx *ctx, const uint8_t *key);   /* five bytes; NULL clears */
+int dprf_ctx_key40(const dprf_ctx *ctx, uint8_t *key);       /* 1 and the five bytes if set, 0 if not */
 
 #ifdef __cplusplus
 }
