@@ -45,6 +45,40 @@ DEVI uint32_t f_maj(uint32_t a, uint32_t b, uint32_t c) {
 }
 DEVI uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
 
+/* The two-input XOR and add in their 8-byte (VOP3) encodings, for the PBKDF2 SHA-1 loops (sha1_compress_pre below).
+ * LLVM emits both as 4-byte VOP2 (_e32); in a loop whose other instructions are all VOP3 (v_alignbit, v_add3,
+ * v_bitop3) every odd count of 4-byte ones leaves the instructions behind it at 4 mod 8, and the dependent pair
+ * v_add3 -> v_xor measured 5 % faster with the _e64 xor (profiles/valu_mix_r04.txt).  With every VALU instruction of
+ * the loop 8 bytes long and the loop's top on a 64-byte line (Makefile SCHED_ODT) k_odt_kdf runs 5.7 % faster
+ * (profiles/ab_sha1_e64.txt).
+ * The xor is v_bitop3 with its second source given twice (full rate: one register read serves both,
+ * profiles/vgpr_bank_r04.txt); a constant operand reaches it in an SGPR.  LLVM shrinks every two-input add it can
+ * see to VOP2, so the add is asm: non-volatile, so it schedules and hoists like any add; both operands are VGPRs
+ * (VOP3 takes no literal on gfx950).  LLVM assumes that a VALU instruction right behind an asm that wrote one of its
+ * sources needs a wait state and puts an s_nop there (4 bytes): callers add the two operands that are ready earliest,
+ * so that the consumer has other work in front of it (sha1_h20_rounds) -- the loops have no s_nop.
+ * SHA1_LOOP_E64 = 0 gives the plain operators and the machine code from before (A/B builds: EXTRA=-DSHA1_LOOP_E64=0). */
+#ifndef SHA1_LOOP_E64
+#define SHA1_LOOP_E64 1
+#endif
+#define LUT_XOR2 0x3C /* src0 ^ src1 */
+DEVI uint32_t xor2_e64(uint32_t a, uint32_t b) {
+#if SHA1_LOOP_E64
+    return __builtin_amdgcn_bitop3_b32(a, b, b, LUT_XOR2);
+#else
+    return a ^ b;
+#endif
+}
+DEVI uint32_t add2_e64(uint32_t a, uint32_t b) {
+#if SHA1_LOOP_E64
+    uint32_t r;
+    asm("v_add_u32_e64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+#else
+    return a + b;
+#endif
+}
+
 /* n / d for any u32 n by a multiply-high with the host's magic for d >= 2 (dprf_host.cpp fastdiv_magic); callers
  * take d = 1 apart.  The one division of every digit step: range_candidate, R5, Agile, R6 and the spelling kernels. */
 DEVI uint32_t fastdiv(uint32_t n, uint32_t m, uint32_t s) {
@@ -142,9 +176,9 @@ template <int T> DEVI uint32_t sha1_h20_word(const uint32_t (&W)[80]) {
     constexpr int f = sha1_h20_form(T);
     uint32_t x;
     if constexpr (in.n == 1) x = W[in.i[0]];
-    else if constexpr (in.n == 2) x = W[in.i[0]] ^ W[in.i[1]];
+    else if constexpr (in.n == 2) x = xor2_e64(W[in.i[0]], W[in.i[1]]);
     else if constexpr (in.n == 3) x = __builtin_amdgcn_bitop3_b32(W[in.i[0]], W[in.i[1]], W[in.i[2]], LUT_XOR3);
-    else x = __builtin_amdgcn_bitop3_b32(W[in.i[0]], W[in.i[1]], W[in.i[2]], LUT_XOR3) ^ W[in.i[3]];
+    else x = xor2_e64(__builtin_amdgcn_bitop3_b32(W[in.i[0]], W[in.i[1]], W[in.i[2]], LUT_XOR3), W[in.i[3]]);
     return rol32(x, f);
 }
 /* rounds T..79, the schedule word of each round computed in front of it; every index is static */
@@ -157,7 +191,11 @@ DEVI void sha1_h20_rounds(uint32_t (&W)[80], uint32_t &a, uint32_t &b, uint32_t 
         else if constexpr (T < 40) { f = xor3(b, c, d);  k = 0x6ED9EBA1u; }
         else if constexpr (T < 60) { f = f_maj(b, c, d); k = 0x8F1BBCDCu; }
         else                       { f = xor3(b, c, d);  k = 0xCA62C1D6u; }
-        const uint32_t tmp = rol32(a, 5) + f + e + (k + W[T]);
+        uint32_t tmp;
+        /* a constant word leaves four addends, a v_add3 and a two-input add (a message word: five, two v_add3); e + f
+         * is known a round before rol(a, 5) is, so the v_add3 never stands right behind the asm (add2_e64) */
+        if constexpr (SHA1_LOOP_E64 && (sha1_h20_zero(T) || sha1_h20_const(T))) tmp = add2_e64(e, f) + rol32(a, 5) + (k + W[T]);
+        else tmp = rol32(a, 5) + f + e + (k + W[T]);
         e = d; d = c; c = rol32(b, 30); b = a; a = tmp;
         sha1_h20_rounds<T + 1>(W, a, b, c, d, e);
     }
@@ -170,6 +208,15 @@ DEVI void sha1_compress_pre(const uint32_t st[5], const sha1_pre_t &P, const uin
 #pragma unroll
     for (int t = 6; t < 15; t++) W[t] = 0;
     W[15] = (64u + 20u) * 8u;
+#if SHA1_LOOP_E64
+    const uint32_t a1 = add2_e64(P.p0, W[0]);
+    const uint32_t a2 = rol32(a1, 5) + P.p1 + W[1];
+    const uint32_t a3 = add2_e64(P.p2, W[2]) + rol32(a2, 5) + f_ch(a1, P.ra, P.rb);
+    const uint32_t r1 = rol32(a1, 30);
+    const uint32_t a4 = add2_e64(P.p3, W[3]) + rol32(a3, 5) + f_ch(a2, r1, P.ra);
+    const uint32_t r2 = rol32(a2, 30);
+    const uint32_t a5 = add2_e64(P.p4, W[4]) + rol32(a4, 5) + f_ch(a3, r2, r1);
+#else
     const uint32_t a1 = P.p0 + W[0];
     const uint32_t a2 = rol32(a1, 5) + P.p1 + W[1];
     const uint32_t a3 = rol32(a2, 5) + f_ch(a1, P.ra, P.rb) + P.p2 + W[2];
@@ -177,9 +224,12 @@ DEVI void sha1_compress_pre(const uint32_t st[5], const sha1_pre_t &P, const uin
     const uint32_t a4 = rol32(a3, 5) + f_ch(a2, r1, P.ra) + P.p3 + W[3];
     const uint32_t r2 = rol32(a2, 30);
     const uint32_t a5 = rol32(a4, 5) + f_ch(a3, r2, r1) + P.p4 + W[4];
+#endif
     uint32_t a = a5, b = a4, c = rol32(a3, 30), d = r2, e = r1;
     sha1_h20_rounds<5>(W, a, b, c, d, e);
-    out[0] = st[0] + a; out[1] = st[1] + b; out[2] = st[2] + c; out[3] = st[3] + d; out[4] = st[4] + e;
+    /* out[0] is no instruction of its own: st[0] joins round 79's second v_add3 (its K + st[0] is loop-invariant) */
+    out[0] = st[0] + a; out[1] = add2_e64(st[1], b); out[2] = add2_e64(st[2], c);
+    out[3] = add2_e64(st[3], d); out[4] = add2_e64(st[4], e);
 }
 DEVI void sha1_iv(uint32_t st[5]) {
     st[0] = SHA1_IV0; st[1] = SHA1_IV1; st[2] = SHA1_IV2; st[3] = SHA1_IV3; st[4] = SHA1_IV4;

@@ -294,7 +294,9 @@ k_odt_kdf(dprf_enum e, dprf_odt_params p, dprf_results *R, uint32_t stop_on_firs
             uint32_t s[5];
             sha1_compress_pre(ist, ipre, u, s);
             sha1_compress_pre(ost, opre, s, u);
-            t[0] ^= u[0]; t[1] ^= u[1]; t[2] ^= u[2]; t[3] ^= u[3]; t[4] ^= u[4];
+            /* two-input ops of the loop in 8-byte encodings (dev_crypto.h xor2_e64) */
+            t[0] = xor2_e64(t[0], u[0]); t[1] = xor2_e64(t[1], u[1]); t[2] = xor2_e64(t[2], u[2]);
+            t[3] = xor2_e64(t[3], u[3]); t[4] = xor2_e64(t[4], u[4]);
         }
         /* each block's key words go out as soon as they are known (block 1's five need not stay live through
          * block 2) */

@@ -79,7 +79,8 @@ k_odf_bf_kdf(dprf_enum e, dprf_odf_params p, dprf_results *R, uint32_t stop_on_f
         uint32_t s[5];
         sha1_compress_pre(ist, ipre, u, s);
         sha1_compress_pre(ost, opre, s, u);
-        t[0] ^= u[0]; t[1] ^= u[1]; t[2] ^= u[2]; t[3] ^= u[3];
+        /* two-input ops of the loop in 8-byte encodings (dev_crypto.h xor2_e64) */
+        t[0] = xor2_e64(t[0], u[0]); t[1] = xor2_e64(t[1], u[1]); t[2] = xor2_e64(t[2], u[2]); t[3] = xor2_e64(t[3], u[3]);
     }
     /* the key bytes are the first 16 of T_1: as BE words they are Blowfish's key words as they stand */
 #pragma unroll
