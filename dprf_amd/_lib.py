@@ -220,8 +220,8 @@ class Context:
     candidate (brute_force.py:163-197).  ``fields``: what parse_verification_data returns -- tag "office" (2007
     Standard and 2010 / 2013 Agile Encryption; kernel families "office_std", "office_agile_sha1",
     "office_agile_sha512"), "oldoffice" (Office 97-2003 RC4 types 0, 1, 3, 4; "office_rc4_md5", "office_rc4_sha1";
-    its ``format`` is FMT_OFFICE too), "odt" ("odf_aes256"), "odf" (ODF 1.0 / 1.1 Blowfish-CFB; "odf_bf_sha1"; its
-    ``format`` is FMT_ODT too) or "pdf" ("pdf_r24", "pdf_r5", "pdf_r6" and their
+    its ``format`` is FMT_OFFICE too), "odt" ("odf_aes256"), "odf" (ODF 1.0 / 1.1 Blowfish-CFB, "odf_bf_sha1", or ODF 1.2 at the
+    manifest's PBKDF2 count, "odf_aes_sha256"; its ``format`` is FMT_ODT too) or "pdf" ("pdf_r24", "pdf_r5", "pdf_r6" and their
     "_owner" families).  ``devices``: a list of HIP ordinals (the library runs one worker
     thread and one stream per entry and splits every call over them); ``device``: one ordinal, or
     ALL_DEVICES for every gfx950 device.  ``pdf_password``: "user" (default) or "owner" -- which of a PDF's two

@@ -755,7 +755,9 @@ def parse_verification_data(stream):
 
     An ODF 1.0 / 1.1 stream (tag "odf", John's odf2john / hashcat 18600 spelling, what odt2hashes prints for a
     Blowfish-CFB package) gives the 12 fields ["odf", "0", "0", iterations, "16", checksum, "8", iv, "16", salt, "0",
-    content]; a ``:::...`` tail is cut off here too."""
+    content]; a ``:::...`` tail is cut off here too.  Its AES spelling (hashcat 18400, what odt2hashes prints for an
+    ODF 1.2 package whose PBKDF2 count is not 1024) gives ["odf", "1", "1", iterations, "32", checksum, "16", iv, "16",
+    salt, "0", content] the same way."""
     print("Preparing verification data...")
     data_array = re.split(r"(?:\*)", stream)
     m = re.search(r".*:\$(\w+)\$", data_array[0])

@@ -246,6 +246,9 @@ constexpr family FAMILIES[K_COUNT] = {
     /* ODF 1.0 / 1.1: half of ODF 1.2's KDF and a check of about the same time again -- its row */
     {K_ODF_BF, "odf_bf_sha1", nullptr, nullptr, nullptr, POLICY_ODT, NO_CUT, 8, 0, false,
      "longer than 64 bytes: long ODF 1.0/1.1 candidates are not supported yet", DPRF_ODF_STREAMS},
+    /* ODF 1.2 at the manifest's iteration count: ODF 1.2's row, which describes 1024 iterations; policy() scales it
+     * by the document's count */
+    {K_ODF_AES, "odf_aes_sha256", nullptr, nullptr, nullptr, POLICY_ODT, NO_CUT, 8, DPRF_LONG_SHA256, true, nullptr, 1},
 };
 constexpr bool rows_in_order(int k = 0) { return k == K_COUNT || (FAMILIES[k].kind == k && rows_in_order(k + 1)); }
 static_assert(rows_in_order(), "FAMILIES needs one row per kernel_kind, in the enum's order");
@@ -255,8 +258,19 @@ const char *kind_name(kernel_kind k, bool owner, bool collide) {
     if (collide && f.collide_name) return f.collide_name;
     return owner && f.owner_name ? f.owner_name : f.name;
 }
-chunk_policy policy(kernel_kind k, bool owner, bool collide) {
+chunk_policy policy(kernel_kind k, bool owner, bool collide, uint32_t iterations) {
     chunk_policy p = fam(k).policy;
+    if (k == K_ODF_AES && iterations && iterations != 1024u) {
+        /* the row is sized for 1024 iterations; a candidate costs iterations / 1024 of that.  Never above hi (the key
+         * buffer holds hi candidates), never below one resident generation of the KDF kernel */
+        auto scale = [&](uint32_t v) {
+            const uint64_t w = round_up(((uint64_t)v * 1024u + iterations - 1) / iterations, p.gran);
+            return (uint32_t)std::min<uint64_t>(p.hi, std::max<uint64_t>(w, ODF_AES_GENERATION));
+        };
+        p.init = scale(p.init);
+        p.lo = scale(p.lo);
+        p.tail = scale(p.tail);
+    }
     if (owner && fam(k).owner_name) p.init = std::max(p.init / 2, p.lo);
     /* a known key: hashing alone, 2 to 5 times the password family's rate (PDF R2 56 G cand/s, type 3
      * 30 G), so the password family's ceiling of 2^30 would hold a launch at 19 to 36 ms of its own 100 ms target.
@@ -266,13 +280,14 @@ chunk_policy policy(kernel_kind k, bool owner, bool collide) {
 }
 uint64_t round_up(uint64_t v, uint64_t g) { return (v + g - 1) / g * g; }
 uint64_t plan_chunk(kernel_kind k, bool owner, double rate, uint64_t remaining, uint64_t total, int ndev, int inflight,
-                    bool collide) {
-    const chunk_policy p = policy(k, owner, collide);
+                    bool collide, uint32_t iterations) {
+    const chunk_policy p = policy(k, owner, collide, iterations);
     uint64_t want = p.init;
     if (rate > 0) {
         const double t = rate * p.target_ms;
         want = p.lo;
         while (want < p.hi && 2.0 * (double)want <= t) want <<= 1;
+        want = std::min<uint64_t>(want, p.hi);   /* a scaled floor is no power of two: the doubling may pass hi */
     }
     if (ndev > 1) {
         const uint64_t nd = (uint64_t)ndev;
@@ -405,11 +420,41 @@ static int parse_odt(dprf_doc *c, const char *const *f) {
 /* ODF 1.0 / 1.1, Blowfish-CFB with SHA-1 (include/dprf.h "ODF 1.0/1.1"): ["odf", cipher "0", checksum type "0",
  * iterations, key size "16", checksum, iv length "8", iv, salt length "16", salt, inplace "0", content].  No reference
  * verifier reads this stream: the hex fields are decoded in full and nothing is flagged. */
+/* ODF 1.2 at the manifest's iteration count (include/dprf.h "$odf$*1*1*"): ["odf", cipher "1", checksum type "1",
+ * iterations, key size "32", checksum, iv length "16", iv, salt length "16", salt, inplace "0", content].  The
+ * reference's own spelling of such a document is the $odt$ stream, which has no field for the count: every refusal
+ * here says so.  Decoded in full, nothing flagged. */
+#define ODF_AES_HINT "; at 1024 iterations the reference's spelling of an ODF 1.2 document is the $odt$ stream (odt2hashes)"
+static int parse_odf_aes(dprf_doc *c, const char *const *f) {
+    static const char *who = "odf (AES-256-CBC, SHA-256)";
+    if (strcmp(f[4], "32")) return fail(DPRF_E_DOMAIN, "%s: key size '%s' (32)" ODF_AES_HINT, who, f[4]);
+    if (strcmp(f[6], "16")) return fail(DPRF_E_DOMAIN, "%s: iv length '%s' (16)" ODF_AES_HINT, who, f[6]);
+    if (strcmp(f[8], "16")) return fail(DPRF_E_DOMAIN, "%s: salt length '%s' (16)" ODF_AES_HINT, who, f[8]);
+    if (strcmp(f[10], "0")) return fail(DPRF_E_DOMAIN, "%s: inplace flag '%s' (0)" ODF_AES_HINT, who, f[10]);
+    uint64_t iter = 0;
+    if (!read_decimal(f[3], 9, 1, DPRF_ODF_MAX_ITER, iter))
+        return fail(DPRF_E_DOMAIN, "%s: iterations '%s' (a decimal in 1..%d)" ODF_AES_HINT, who, f[3], DPRF_ODF_MAX_ITER);
+    uint8_t ck[32], iv[16], salt[16];
+    std::vector<uint8_t> content(4 * DPRF_ODF_CONTENT_WORDS);
+    const struct { int at; size_t n; uint8_t *out; const char *what; } hex[4] = {
+        {5, 32, ck, "checksum"}, {7, 16, iv, "iv"}, {9, 16, salt, "salt"}, {11, content.size(), content.data(), "content"}};
+    for (const auto &h : hex)
+        if (const int r = decode_hex_exact(f[h.at], h.n, h.out, h.what, who))
+            return fail(r, "%s" ODF_AES_HINT, std::string(dprf_last_error()).c_str());
+    for (int i = 0; i < 8; i++) c->odt.checksum[i] = be_word(&ck[4 * i]);
+    for (int i = 0; i < 4; i++) c->odt.iv[i] = be_word(&iv[4 * i]);
+    for (int i = 0; i < 4; i++) c->odt.salt[i] = c->odfaes.salt[i] = be_word(&salt[4 * i]);
+    c->odt.enc_len = c->odt.hash_len = 4 * DPRF_ODF_CONTENT_WORDS;
+    c->odfaes.iterations = (uint32_t)iter;
+    c->odt_words.assign(DPRF_ODF_CONTENT_WORDS, 0u);
+    for (int i = 0; i < DPRF_ODF_CONTENT_WORDS; i++) c->odt_words[i] = be_word(&content[4 * i]);
+    c->kind = K_ODF_AES;
+    return DPRF_OK;
+}
+
 static int parse_odf(dprf_doc *c, const char *const *f) {
     static const char *who = "odf";
-    if (!strcmp(f[1], "1") && !strcmp(f[2], "1"))
-        return fail(DPRF_E_DOMAIN, "odf: cipher 1 / checksum type 1 is AES-256 with SHA-256: ODF 1.2 documents go in as "
-                                   "the $odt$ stream (odt2hashes)");
+    if (!strcmp(f[1], "1") && !strcmp(f[2], "1")) return parse_odf_aes(c, f);
     if (strcmp(f[1], "0")) return fail(DPRF_E_DOMAIN, "odf: cipher '%s' (0: Blowfish-CFB)", f[1]);
     if (strcmp(f[2], "0")) return fail(DPRF_E_DOMAIN, "odf: checksum type '%s' (0: SHA-1)", f[2]);
     if (strcmp(f[4], "16")) return fail(DPRF_E_DOMAIN, "odf: key size '%s' (16)", f[4]);
@@ -593,6 +638,8 @@ int check_key40_domain(const dprf_doc *c) {
             return fail(DPRF_E_DOMAIN, "40-bit key search: Office 2010/2013 Agile Encryption is AES under a spun hash, not "
                         "a 40-bit document");
         case K_ODT:
+            return fail(DPRF_E_DOMAIN, "40-bit key search: ODF 1.2 is AES-256 under PBKDF2, not a 40-bit document");
+        case K_ODF_AES:
             return fail(DPRF_E_DOMAIN, "40-bit key search: ODF 1.2 is AES-256 under PBKDF2, not a 40-bit document");
         case K_ODF_BF:
             return fail(DPRF_E_DOMAIN, "40-bit key search: ODF 1.0/1.1 is Blowfish with a 128-bit PBKDF2 key, not a 40-bit "

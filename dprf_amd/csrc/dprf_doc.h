@@ -39,7 +39,7 @@ int fail(int code, const char *fmt, ...);
 
 /* ------------------------------------------------------------------ kernel families */
 enum kernel_kind { K_NONE, K_OFFICE, K_ODT, K_PDF_R24, K_PDF_R5, K_PDF_R6, K_AGILE_SHA1, K_AGILE_SHA512,
-                   K_OLDOFFICE_MD5, K_OLDOFFICE_SHA1, K_ODF_BF, K_COUNT };
+                   K_OLDOFFICE_MD5, K_OLDOFFICE_SHA1, K_ODF_BF, K_ODF_AES, K_COUNT };
 
 /* Candidates per launch.  A device takes its next chunk from the call's shared cursor sized for about
  * `target_ms` of device time at the rate it measured on its last launch (`init` before the first), a
@@ -77,10 +77,17 @@ const char *kind_name(kernel_kind k, bool owner = false, bool collide = false);
  * policy with the first chunk halved (the measured rate sizes the later ones).
  * collide: a known key is set (dprf_ctx_set_key40) and the password searches run the collider kernels, hashing only:
  * the password family's policy (dprf_doc.cpp policy() says what differs) */
-chunk_policy policy(kernel_kind k, bool owner = false, bool collide = false);
+/* iterations: the PBKDF2 count of a K_ODF_AES document (plan_iterations), 0 for every other one.  That family's row
+ * describes 1024 iterations: the first launch, the floor and the tail scale by 1024 / iterations, rounded up to the
+ * granularity, never above `hi` (the key buffer) nor below ODF_AES_GENERATION.  Past 1638 iterations the floor is no
+ * power of two any more, so plan_chunk holds its doubling to `hi`. */
+chunk_policy policy(kernel_kind k, bool owner = false, bool collide = false, uint32_t iterations = 0);
 uint64_t round_up(uint64_t v, uint64_t g);
 uint64_t plan_chunk(kernel_kind k, bool owner, double rate, uint64_t remaining, uint64_t total, int ndev, int inflight,
-                    bool collide = false);
+                    bool collide = false, uint32_t iterations = 0);
+/* One resident generation of k_odf_aes_kdf at the occupancy it builds with: 256 CUs x 4 SIMDs x 5 waves x 64 lanes
+ * (ODF_AES_KDF_WAVES where the kernel is defined) */
+static const uint32_t ODF_AES_GENERATION = 256u * 4u * 5u * 64u;
 /* The key search of a family (dprf_search_key40) plans with the password family's policy, owner = false: the measured
  * rate sizes the later chunks.  Its name, or null when the family has no 40-bit documents. */
 inline const char *key40_name(kernel_kind k) { return fam(k).key40_name; }
@@ -101,12 +108,17 @@ struct dprf_doc {
     std::vector<uint32_t> odt_words;  /* first min(len,1024) ciphertext bytes, BE words */
     dprf_odf_params odf{};            /* ODF 1.0 / 1.1 Blowfish (K_ODF_BF) */
     std::vector<uint32_t> odf_words;  /* iv || content[0:1024], BE words: the E_key inputs and the ciphertext in one run */
+    dprf_odf_aes_params odfaes{};     /* ODF 1.2 at the manifest's count (K_ODF_AES): the KDF's half; odt / odt_words
+                                         hold the check's */
     dprf_long_params lp{};            /* the long-list prehash of the format (set_long_params) */
     /* the word table of hybrid searches (dprf_ctx_set_words; the lanes hold the bytes): its size, and its longest
      * word before the clip to a slot, which decides whether a mask fits */
     uint64_t nwords = 0;
     uint64_t w_longest = 0, w_longest_idx = 0;
 };
+
+/* What policy() and plan_chunk() take as `iterations` for this document */
+inline uint32_t plan_iterations(const dprf_doc *d) { return d->kind == K_ODF_AES ? d->odfaes.iterations : 0u; }
 
 /* The field array of dprf_ctx_create: parse_verification_data's accepted shapes (brute_force.py:253-260) by tag and
  * field count, the tag's parser, and on success the long-list parameters.  Fills fmt, flags, kind and the params. */

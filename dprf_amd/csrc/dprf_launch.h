@@ -23,6 +23,11 @@ hipError_t launch_odf(const dprf_enum &e, const dprf_odf_params &p, dprf_results
 hipError_t launch_odt(const dprf_enum &e, const dprf_odt_params &p, const dprf_aes_tables *T,
                       dprf_results *R, uint32_t cap, uint32_t stop, hipStream_t s, uint32_t *keys,
                          hipEvent_t mid);
+/* ODF 1.2 at the manifest's iteration count (dprf_kernels_odfaes.hip): its own KDF with kp, then launch_odt's check
+ * kernel with p, eight key words per candidate in `keys`; e.mode 0, 1 or 2 */
+hipError_t launch_odf_aes(const dprf_enum &e, const dprf_odf_aes_params &kp, const dprf_odt_params &p,
+                          const dprf_aes_tables *T, dprf_results *R, uint32_t cap, uint32_t stop, hipStream_t s,
+                          uint32_t *keys, hipEvent_t mid);
 hipError_t launch_pdf_r5(const dprf_enum &e, const dprf_pdf_params &p, dprf_results *R, uint32_t cap,
                          uint32_t stop, hipStream_t s);
 hipError_t launch_pdf_r24(const dprf_enum &e, const dprf_pdf_params &p, dprf_results *R, uint32_t cap,

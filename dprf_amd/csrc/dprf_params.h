@@ -181,6 +181,13 @@ struct dprf_odf_params {
                                        pt_i = (x[2i + 2], x[2i + 3]) ^ E_key(x[2i], x[2i + 1]), i = 0..127 */
 };
 
+/* ODF 1.2 at the manifest's iteration count (include/dprf.h "$odf$*1*1*"): what k_odf_aes_kdf reads of the document.
+ * The check is k_odt_check's, on a dprf_odt_params with enc_len = hash_len = 1024. */
+struct dprf_odf_aes_params {
+    uint32_t salt[4];               /* BE */
+    uint32_t iterations;            /* PBKDF2 count, 1..DPRF_ODF_MAX_ITER */
+};
+
 /* PDF: pdf_password_verifier.c:64-291 */
 #define DPRF_PDF_TAIL_WORDS 64
 #define DPRF_PDF_OSUF_WORDS 14

@@ -45,6 +45,7 @@ SCRATCH_LIMIT = {
     "k_key40_oldoffice": 0,
     "k_collide_pdf": 0,       # password for a known 40-bit key (dprf_ctx_set_key40): PDF R2-R4, Office 97-2003
     "k_collide_oldoffice": 0,
+    "k_odf_aes_kdf": 0,       # ODF 1.2 at the manifest's iteration count (dprf_kernels_odfaes.hip); its check is k_odt_check
 }
 
 

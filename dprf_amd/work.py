@@ -265,6 +265,23 @@ MAIN = {
     "odt_e": {"sha256c": 1, "sha1c": 4, "sha1c_hmac20": 4094},
     "odf_legacy": {"sha1c": 3, "sha1c_hmac20": 2048},
 }
+
+
+def odf_aes_counts(iterations, sha256_blocks=1):
+    """Primitive counts per candidate of the ``$odf$*1*1*`` stream (family odf_aes_sha256; no bench.py workload) as
+    a function of its PBKDF2 count c: (COUNTS row, MAIN row).  SHA256(pw) is 1 compression up to 55 bytes and 2 from
+    56 (``sha256_blocks``), the 1 KiB checksum 17.  PBKDF2 is the ipad/opad midstates 2 + 2 blocks x c iterations x 2
+    = 2 + 4c SHA-1 compressions.  As in COUNTS["odt"], the row this equals at c = 1024, the midstates and the two
+    compressions of salt || INT(i) are plain sha1c (4) and the 4c - 2 whose 20-byte message is a digest are
+    sha1c_hmac20."""
+    c = int(iterations)
+    if c < 1 or sha256_blocks not in (1, 2):
+        raise ValueError("iterations %r / sha256_blocks %r" % (iterations, sha256_blocks))
+    main = {"sha256c": sha256_blocks, "sha1c": 4, "sha1c_hmac20": 4 * c - 2}
+    counts = dict(main, sha256c=sha256_blocks + 17, aes256_dec_block=64, aes256_keyexp_dec_sched=1)
+    return counts, main
+
+
 # which resource bounds each format when no current rocprof profile says otherwise.  The RC4 formats saturate
 # neither pipe (R3/R4 VALUBusy 0.73, LdsUtil 0.52: each wave's KSA is a chain of one dependent LDS round trip per
 # two steps, DESIGN.md section 6); VALU is the busier of the two, so that is what their fraction is quoted against.

@@ -39,7 +39,8 @@ extern "C" {
                                "$office$*2013*..." Agile Encryption (below); "$oldoffice$..."
                                Office 97-2003 RC4 / RC4 CryptoAPI (below)                    */
 #define DPRF_FMT_ODT 2      /* "$odt$*1.2*..."      ODF 1.2 AES-256-CBC / PBKDF2-HMAC-SHA1;
-                               "$odf$*0*0*..."      ODF 1.0 / 1.1 Blowfish-CFB, SHA-1 (below)  */
+                               "$odf$*0*0*..."      ODF 1.0 / 1.1 Blowfish-CFB, SHA-1 (below);
+                               "$odf$*1*1*..."      ODF 1.2 at the manifest's PBKDF2 count (below)  */
 #define DPRF_FMT_PDF 3      /* "$pdf$*V*R*..."      PDF standard security handler R2..R6       */
 
 /* error codes */
@@ -246,16 +247,47 @@ int dprf_ctx_last_call_devices(const dprf_ctx *ctx, dprf_device_stats *out, int 
  * Accepted domain, anything else DPRF_E_DOMAIN with a message naming the field: cipher "0" and checksum type "0"; key
  * size "16", IV length "8", salt length "16", inplace "0"; the hex fields of exactly the lengths above; iterations a
  * decimal in 1..DPRF_ODF_MAX_ITER (a kernel argument; real files say 1024).  The AES spelling of the same stream,
- * "$odf$*1*1*...", is refused with a message saying that ODF 1.2 documents go in as "$odt$".  Such a context sets no
+ * "$odf$*1*1*...", is the next section's; the mixed pairs (cipher 1 with checksum type 0, and the reverse) are
+ * refused.  Such a context sets no
  * flag; dprf_ctx_set_pdf_password on it is DPRF_E_INVALID.  dprf_ctx_kernel returns "odf_bf_sha1", a family
  * dprf_plan_chunk knows: a caller detects the support with dprf_plan_chunk("odf_bf_sha1", 0, 1, 1, 1, 0) != 0
  * (DPRF_ABI_VERSION is unchanged: no export or struct changed).  Range, symbol, mask, list, hybrid and rule modes work
  * as for the "$odt$" stream (raw bytes, rule unit = byte), except that a list candidate over the 64-byte slot is
  * DPRF_E_PWLEN, reported per candidate by dprf_list_status: long ODF 1.0/1.1 candidates are not supported yet.
  * Not done: content shorter than 1024 bytes (old OpenOffice builds wrote a defective SHA-1 for some lengths),
- * StarOffice / OpenOffice.org 1.x packages (.sxw, .sxc), the "$odf$*1*1*" spelling, candidates over 64 bytes,
- * decrypting the document. */
+ * StarOffice / OpenOffice.org 1.x packages (.sxw, .sxc), candidates over 64 bytes, decrypting the document (the
+ * "$odf$*1*1*" spelling is done: below). */
 #define DPRF_ODF_MAX_ITER 10000000
+
+/* ---- ODF 1.2 at the manifest's iteration count: AES-256-CBC, SHA-256, PBKDF2 with any count (LibreOffice 3.5 to
+ * 5.x wrote 1024, LibreOffice since then writes 100000) ----
+ * The "$odt$" stream above has no field for the PBKDF2 count, and the reference verifier runs 1024 whatever the manifest
+ * says (odt_password_verifier.c:85).  The stream that carries the count is the AES spelling of the stream of the last
+ * section, John's odf2john / hashcat mode 18400; odt2hashes.py prints it for an AES-256-CBC package whose count is not
+ * 1024:
+ *   $odf$*1*1*<iterations>*32*<checksum, 64 hex>*16*<iv, 32 hex>*16*<salt, 32 hex>*0*<content, 2048 hex>
+ * cipher 1 = AES-256-CBC, checksum type 1 = SHA-256, key size 32, IV length 16, salt length 16, inplace 0, and the first
+ * 1024 bytes of the encrypted entry.  dprf_ctx_create takes fields[0] == "odf" with nfields == 12: ["odf", "1", "1",
+ * iterations, "32", checksum, "16", iv, "16", salt, "0", content].  dprf_ctx_format returns DPRF_FMT_ODT.
+ *   sk  = SHA256(pw)                                   pw: the candidate's bytes as given
+ *   key = PBKDF2-HMAC-SHA1(P = sk (32 bytes), S = salt, c = iterations, dkLen = 32)        (two output blocks)
+ *   pt  = AES-256-CBC-decrypt(key, iv, content[0:1024])
+ *   the candidate verifies when SHA256(pt) == checksum, all 32 bytes
+ * At iterations = 1024 this is the "$odt$" stream's check of a document of at least 1024 encrypted bytes, and the two
+ * contexts report the same hits.  No public test vector of this stream is at hand: the definition rests on the model of
+ * tests/test_odf12_iter_model.py (hashlib's SHA-256 and PBKDF2, the test generator's AES-CBC), whose verdicts at
+ * iterations = 1024 equal the oracle's and the reference verifier's on the "$odt$" stream of the same document.
+ * Accepted domain, anything else DPRF_E_DOMAIN with a message naming the field (and, since the reference's own spelling
+ * of such a document is "$odt$", saying so): key size "32", IV length "16", salt length "16", inplace "0"; the hex
+ * fields of exactly the lengths above; iterations a decimal in 1..DPRF_ODF_MAX_ITER (a kernel argument).  Such a
+ * context sets no flag.  dprf_ctx_kernel returns "odf_aes_sha256", a family dprf_plan_chunk knows: a caller detects the
+ * support with dprf_plan_chunk("odf_aes_sha256", 0, 1, 1, 1, 0) != 0 (DPRF_ABI_VERSION is unchanged: no export or struct
+ * changed).  dprf_plan_chunk answers for 1024 iterations; a context plans its own launches by its count (the first
+ * launch, the floor and the tail are the row's times 1024 / iterations, never below one resident generation of the KDF
+ * kernel).  Range, symbol, mask, list, hybrid and rule modes work as for the "$odt$" stream (raw bytes, rule unit =
+ * byte), list candidates of any length included.
+ * Not done: Argon2id key derivation and AES-256-GCM (LibreOffice 24.2's optional "wholesome" encryption), content shorter
+ * than 1024 bytes, decrypting the document. */
 
 /* ---- owner password (ABI 9): which of a PDF's two passwords the searches verify ----
  * A PDF carries a user password (opens the document) and an owner password (lifts the print / copy / edit
