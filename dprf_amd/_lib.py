@@ -27,7 +27,8 @@ EXPORTS = ["dprf_abi_version", "dprf_last_error", "dprf_device_count", "dprf_dev
            "dprf_ctx_devices", "dprf_search_range", "dprf_verify_list", "dprf_list_status", "dprf_build_id",
            "dprf_plan_chunk", "dprf_ctx_last_call_devices", "dprf_search_symbols", "dprf_search_mask",
            "dprf_ctx_set_pdf_password", "dprf_ctx_pdf_password", "dprf_ctx_set_words", "dprf_ctx_words",
-           "dprf_words_status", "dprf_search_hybrid", "dprf_search_rules", "dprf_spell_rules"]
+           "dprf_words_status", "dprf_search_hybrid", "dprf_search_rules", "dprf_spell_rules",
+           "dprf_ctx_set_right_words", "dprf_ctx_right_words", "dprf_search_combine", "dprf_spell_combine"]
 # additive to ABI 9: a caller looks these up, a library without them still loads (include/dprf.h "40-bit key search",
 # "password for a known key").  Apart from EXPORTS, which is the ABI 9 baseline that every library has.
 ADDITIVE_EXPORTS = ["dprf_search_key40", "dprf_ctx_set_key40", "dprf_ctx_key40"]
@@ -155,6 +156,24 @@ def lib():
                 L.dprf_ctx_set_key40.restype = ctypes.c_int
                 L.dprf_ctx_key40.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
                 L.dprf_ctx_key40.restype = ctypes.c_int
+            # combinator mode (include/dprf.h "combinator mode").  The contract is the header's: additive to ABI 9,
+            # detected by symbol lookup, so a libdprf.so built before them (DPRF_LIB) still loads and the four
+            # methods say what is missing (_combine_export).  The names stand in EXPORTS all the same, as the hybrid
+            # and rule exports do: EXPORTS lists what include/dprf.h declares (tests/test_abi.py), not what an older
+            # library has.
+            if hasattr(L, "dprf_search_combine"):
+                L.dprf_ctx_set_right_words.argtypes = [ctypes.c_void_p, ctypes.c_char_p,
+                                                       ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64]
+                L.dprf_ctx_set_right_words.restype = ctypes.c_int
+                L.dprf_ctx_right_words.argtypes = [ctypes.c_void_p]
+                L.dprf_ctx_right_words.restype = ctypes.c_int64
+                L.dprf_search_combine.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64,
+                                                  ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Stats)]
+                L.dprf_search_combine.restype = ctypes.c_int
+                L.dprf_spell_combine.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                                 ctypes.c_void_p]
+                L.dprf_spell_combine.restype = ctypes.c_int
             if L.dprf_abi_version() != ABI_VERSION:
                 raise ImportError("libdprf.so ABI %d != %d" % (L.dprf_abi_version(), ABI_VERSION))
             _lib = L
@@ -491,6 +510,54 @@ class Context:
     def spell_rules(self, rules, start, count):
         """spell_rules_raw as a list of bytes, one candidate each."""
         slots, lens = self.spell_rules_raw(rules, start, count)
+        raw = slots.tobytes()
+        return [raw[64 * k:64 * k + int(lens[k])] for k in range(len(lens))]
+
+    @staticmethod
+    def _combine_export(name):
+        export = getattr(lib(), name, None)
+        if export is None:
+            raise DprfError(E_INVALID, "this libdprf.so has no %s: rebuild it" % name)
+        return export
+
+    def set_right_words(self, words):
+        """The right table of combinator searches (include/dprf.h dprf_ctx_set_right_words): as set_words, which sets
+        the left one; neither touches the other.  An empty sequence clears it.  DprfError(E_DOMAIN) for an empty word,
+        a NUL or (Office) invalid UTF-8, (E_INVALID) for 2^31 words or more; the previous table stays then."""
+        blob, offs = self._word_blob(words)
+        _check(self._combine_export("dprf_ctx_set_right_words")(
+            self._h, blob, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(offs) - 1))
+
+    @property
+    def right_words(self):
+        """The number of right words the context holds (0: no table)."""
+        n = self._combine_export("dprf_ctx_right_words")(self._h)
+        if n < 0:
+            _check(int(n))
+        return int(n)
+
+    def search_combine(self, start, count, stop_on_first=False, cap=1 << 16):
+        """Verify keyspace indices [start, start+count) of left words x right words: index i is left word i // N2
+        followed by right word i % N2 (N2 right words), spelled on the device (include/dprf.h dprf_search_combine).
+        Returns (sorted hit indices -- keyspace indices --, total hits, stats dict)."""
+        start, count = _check_window(start, count)
+        return self._call(self._combine_export("dprf_search_combine"), (start, count), stop_on_first, cap, start)
+
+    def spell_combine_raw(self, start, count):
+        """The candidates [start, start+count) of left x right as the device spells them: (slots, lens), numpy uint8
+        arrays of shape (count, 64) and (count,), exactly what search_combine would verify (after the format's cut;
+        Office: UTF-16LE).  No verification runs (include/dprf.h dprf_spell_combine; count <= 2^20)."""
+        import numpy as np
+        start, count = _check_window(start, count)
+        room = max(1, min(count, MAX_SPELL))              # the library refuses a larger count before it writes
+        slots = np.zeros((room, 64), dtype=np.uint8)
+        lens = np.zeros(room, dtype=np.uint8)
+        _check(self._combine_export("dprf_spell_combine")(self._h, start, count, slots.ctypes.data, lens.ctypes.data))
+        return slots[:count], lens[:count]
+
+    def spell_combine(self, start, count):
+        """spell_combine_raw as a list of bytes, one candidate each."""
+        slots, lens = self.spell_combine_raw(start, count)
         raw = slots.tobytes()
         return [raw[64 * k:64 * k + int(lens[k])] for k in range(len(lens))]
 

@@ -30,6 +30,9 @@ candidates go to libdprf.so in batches, one candidate per GPU lane.  Differences
 * rule mode (an extension; ``rules``, ``--rules``): every word of a wordlist under every rule of one or two rule files
   (:mod:`dprf_amd.rules`: "c $1", "sa@ so0"), applied on the device -- :func:`init_rules_brute_force`; ``--stdout``
   prints the candidates instead of verifying them.
+* combinator mode (an extension; ``wordlist2``, ``--wordlist2``): every word of a wordlist followed by every word of a
+  second one (:mod:`dprf_amd.combine`: "summer" + "2024"), with one rule per side (``--rule-left '$-'``) applied while
+  the two tables are built -- :func:`init_combine_brute_force`; ``--stdout`` prints the candidates here too.
 * 40-bit key search (an extension; ``--key40``): for the documents that carry only 40 bits of RC4 key (PDF R2, R3/R4
   with Length 40, Office 97-2003 types 0 / 1 / 3) the keys themselves are searched, all 2^40 of them or a window
   (:mod:`dprf_amd.key40`) -- :func:`init_key40_brute_force`.  It reports the key, not a password.
@@ -49,6 +52,7 @@ import textwrap
 import time
 
 from . import _lib
+from . import combine
 from . import hybrid
 from . import key40
 from . import mask as masks
@@ -71,13 +75,23 @@ OFFICE_TAGS = ("office", "oldoffice")   # the streams of document type 1: their 
 
 
 def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, checkpoint=None, mask=None,
-         custom_charsets=(), owner=False, wordlist=None, rules=None, key=None):
+         custom_charsets=(), owner=False, wordlist=None, rules=None, key=None, wordlist2=None, rule_left=None,
+         rule_right=None):
     # The common entry point (brute_force.py:39-57)
     if key is not None:
         # a known 40-bit key (--key): every candidate source verifies against it (key40.known_key spells it)
         if owner:
             raise ValueError('A password for a known key is a user password (--key cannot be combined with --owner).')
         key = key40.known_key(key)
+    if wordlist2 is not None:
+        # combinator mode: two wordlists and nothing else beside them but one rule per side
+        if wordlist is None:
+            raise ValueError('--wordlist2 is the right side of a combinator search: it needs a --wordlist, the left side.')
+        if rules is not None or mask not in (None, "?w"):
+            raise ValueError('--wordlist2 cannot be combined with --mask or --rules (a rule per side: --rule-left, '
+                             '--rule-right).')
+    elif rule_left is not None or rule_right is not None:
+        raise ValueError('--rule-left and --rule-right belong to a combinator search (--wordlist2).')
     if rules is not None:
         # rule mode: a wordlist and nothing else beside the rules
         if wordlist is None:
@@ -108,6 +122,9 @@ def init(stream, password_range, passwords, charset=LOWERCASE, devices=None, che
     print("Initializing brute-force.")
 
     try:
+        if wordlist2 is not None:
+            return init_combine_brute_force(input_data, wordlist, wordlist2, rule_left=rule_left, rule_right=rule_right,
+                                            devices=devices, checkpoint=checkpoint, owner=owner, key=key)
         if rules is not None:
             return init_rules_brute_force(input_data, wordlist, rules, devices=devices, checkpoint=checkpoint,
                                           owner=owner, key=key)
@@ -177,12 +194,14 @@ class Checkpoint:
     and their number) keeps its mask under a name of its own beside them, so it loads no mask search's file, no mask
     search loads its file, and a changed wordlist is refused.  A rule search (rules: the SHA-256 of its encoded rules
     and their number) adds those to the hybrid key of the bare word, so a changed rule file is refused like a changed
-    wordlist and neither search loads the other's file.  A password search against a known key carries "target":
+    wordlist and neither search loads the other's file.  A combinator search (wordlist2) records "search": "combine",
+    both wordlists' SHA-256 and word counts and the text of both side rules, so a changed file or rule is refused.  A
+    password search against a known key carries "target":
     "key40:" and the key's ten hex digits, so it loads no other key's file and no document search's.  A 40-bit key search (key_window: its first and last key
     index) records "search": "key40" and the window; its cursor is a key index and `found` the key's hex digits."""
 
     def __init__(self, path, input_data, charset=None, pwlen=None, mask=None, custom=(), target="user",
-                 wordlist=None, rules=None, key_window=None):
+                 wordlist=None, rules=None, key_window=None, wordlist2=None, side_rules=None):
         import hashlib
         self.path = path
         self.target = target
@@ -191,6 +210,12 @@ class Checkpoint:
             # a 40-bit key search: the cursor is a key index; the key names the search and its window, so neither a
             # password search's file nor another window's loads
             self.key.update(search="key40", window=[int(key_window[0]), int(key_window[1])])
+        elif wordlist2 is not None:
+            # a combinator search: both wordlists and both side rules (their text, "" for none); it has no hybrid
+            # mask and names itself, so neither a hybrid search nor this one loads the other's file
+            self.key.update(search="combine", wordlist_sha256=wordlist[0], words=int(wordlist[1]),
+                            wordlist2_sha256=wordlist2[0], words2=int(wordlist2[1]),
+                            rule_left=(side_rules or ("", ""))[0], rule_right=(side_rules or ("", ""))[1])
         elif wordlist is not None:
             self.key.update(hybrid_mask=mask, custom=[c or "" for c in custom], wordlist_sha256=wordlist[0],
                             words=int(wordlist[1]))
@@ -648,6 +673,114 @@ def print_rule_candidates(input_data, wordlist, rules, devices=None, out=None):
         ctx.close()
 
 
+def _side_rule(rule):
+    """A side rule of combinator mode as (parsed rule or None, its text for the checkpoint): None, rule text (str or
+    bytes), or a parsed rule."""
+    if rule is None:
+        return None, ""
+    parsed = rulemod.parse_rule(rule) if isinstance(rule, (str, bytes)) else tuple(rule)
+    return parsed, rulemod.format_rule(parsed).decode("latin-1")
+
+
+def _combine_tables(ctx, input_data, left, right, rule_left, rule_right):
+    """The two tables a combinator search keeps, printing what it drops: words no candidate can contain, words a side
+    rule does not take, and -- where the format cuts behind more than 64 bytes -- the longer words of each side, by the
+    pair of limits combine.fit picks.  The side rules are applied here, once per word."""
+    office = input_data[0] in OFFICE_TAGS
+    sides = []
+    for name, words, rule in (("--wordlist", left, rule_left), ("--wordlist2", right, rule_right)):
+        status = ctx.words_status(words)
+        bad = [k for k in range(len(words)) if status[k] != 0]
+        if bad:
+            print("Dropped %d words no candidate can contain (empty, a NUL byte, or for Office invalid UTF-8), the "
+                  "first is word %d (%s)" % (len(bad), bad[0] + 1, name))
+            words = [w for k, w in enumerate(words) if status[k] == 0]
+        words, lost = combine.apply_side_rule(rule, words, office)
+        if lost:
+            print("Dropped %d words the rule of %s does not apply to (over 64 bytes, or its result is no text)"
+                  % (lost, name))
+        sides.append(words)
+    left, right = sides
+    if not ctx.kernel.startswith("pdf_r24"):                  # R2-R4 cut at 32 bytes: every pair fits
+        wide = (lambda b: len(b.decode("utf-8").encode("utf-16-le"))) if office else len
+        ll, rl = [wide(w) for w in left], [wide(w) for w in right]
+        if ll and rl and max(ll) + max(rl) > combine.SLOT:
+            a, b = combine.fit(ll, rl)
+            nl, nr = sum(1 for n in ll if n > a), sum(1 for n in rl if n > b)
+            print("Dropped %d left words over %d bytes and %d right words over %d bytes: two words share a 64-byte "
+                  "candidate; the pairs with a dropped word are not searched" % (nl, a, nr, b))
+            left = [w for w, n in zip(left, ll) if n <= a]
+            right = [w for w, n in zip(right, rl) if n <= b]
+    return left, right, office
+
+
+def _read_words(wordlist):
+    return hybrid.read_wordlist(wordlist) if isinstance(wordlist, str) else [hybrid._bytes(w) for w in wordlist]
+
+
+def init_combine_brute_force(input_data, wordlist, wordlist2, rule_left=None, rule_right=None, devices=None,
+                             checkpoint=None, owner=False, key=None):
+    """Every word of `wordlist` followed by every word of `wordlist2` (dprf_amd.combine), left words in file order,
+    per left word the right words in file order, plus "_dummy" first as in range mode: the same rounds as hybrid mode,
+    one ctx.search_combine call each with stop_on_first, so the lowest keyspace index that verifies wins.  Each
+    wordlist is a file path or a sequence of bytes words; rule_left / rule_right: one rule of dprf_amd.rules (text or
+    parsed) applied once to every word of that side while the tables are built.  Both tables go to the devices once;
+    the candidates are spelled there.  checkpoint: keyed by both wordlists' SHA-256 and word counts and both rules."""
+    left, right = _read_words(wordlist), _read_words(wordlist2)
+    rl, rl_text = _side_rule(rule_left)
+    rr, rr_text = _side_rule(rule_right)
+    cp = Checkpoint(checkpoint, input_data, target=_target(owner, key), wordlist=wordlist_key(left),
+                    wordlist2=wordlist_key(right), side_rules=(rl_text, rr_text))
+
+    def begin(ctx):
+        lw, rw, _ = _combine_tables(ctx, input_data, left, right, rl, rr)
+        space = combine.space(len(lw), len(rw))
+
+        def search(start, n):
+            hits, _, st = ctx.search_combine(start, n, stop_on_first=True, cap=1)
+            return (hits[0] if hits else None), st
+
+        def run(rounds, done, t0):
+            if space:
+                ctx.set_words(lw)
+                ctx.set_right_words(rw)
+            return rounds(done, space, search, lambda idx: hybrid.text(combine.candidate(lw, rw, idx)))
+
+        return run
+
+    return _resumable_search(input_data, cp, devices, owner, begin, key=key)
+
+
+def print_combine_candidates(input_data, wordlist, wordlist2, rule_left=None, rule_right=None, devices=None, out=None):
+    """--stdout: the candidates of a combinator search as the device spells them (ctx.spell_combine: after the format's
+    cut), one per line, decoded as found passwords are (:func:`rule_text`).  Verifies nothing.  Returns their number."""
+    out = sys.stdout if out is None else out
+    left, right = _read_words(wordlist), _read_words(wordlist2)
+    rl, rr = _side_rule(rule_left)[0], _side_rule(rule_right)[0]
+    ctx = _lib.Context(input_data, devices=_devices(devices)[:1])
+    try:
+        lw, rw, office = _combine_tables(ctx, input_data, left, right, rl, rr)
+        space = combine.space(len(lw), len(rw))
+        if not space:
+            return 0
+        ctx.set_words(lw)
+        ctx.set_right_words(rw)
+        raw = getattr(out, "buffer", None)
+        for start in range(0, space, _lib.MAX_SPELL):
+            lines = [rule_text(cand, office).encode("utf-8", "surrogatepass" if office else "surrogateescape")
+                     for cand in ctx.spell_combine(start, min(_lib.MAX_SPELL, space - start))]
+            data = b"\n".join(lines) + b"\n"
+            if raw is not None:                   # the candidates' own bytes, valid UTF-8 or not
+                out.flush()
+                raw.write(data)
+                raw.flush()
+            else:
+                out.write(data.decode("utf-8", "replace"))
+        return space
+    finally:
+        ctx.close()
+
+
 def _time_left(seconds):
     seconds = int(seconds)
     if seconds >= 86400:
@@ -828,8 +961,16 @@ def main(argv=None):
                         help="rule search: every word of the --wordlist under every rule of this file (one rule per "
                              "line, hashcat's functions : l u c C t TN E r d pN f { } q k K *NM $X ^X [ ] DN xNM ONM iNX "
                              "oNX 'N zN ZN yN YN sXY @X .N ,N); given twice, the two files are multiplied")
+    parser.add_argument("--wordlist2", default=None, metavar="RIGHT",
+                        help="combinator search: every word of --wordlist followed by every word of this file (i.e., "
+                             "summer + 2024); not with --mask, --rules, -pr or --key40")
+    parser.add_argument("--rule-left", dest="rule_left", default=None, metavar="RULE",
+                        help="with --wordlist2: one rule (the functions of --rules) applied to every word of --wordlist "
+                             "(i.e., '$-' for a separator)")
+    parser.add_argument("--rule-right", dest="rule_right", default=None, metavar="RULE",
+                        help="with --wordlist2: one rule applied to every word of --wordlist2")
     parser.add_argument("--stdout", action="store_true",
-                        help="with --rules: print the candidates, one per line, and verify nothing")
+                        help="with --rules or --wordlist2: print the candidates, one per line, and verify nothing")
     parser.add_argument("--owner", action="store_true",
                         help="search the PDF's owner password (the one that lifts print / copy / edit restrictions) "
                              "instead of its user password; document type 3 only")
@@ -848,6 +989,7 @@ def main(argv=None):
     if args.key40 is not None:
         for flag, given in (("-pr/--passwordrange", args.passwordrange is not None), ("--charset", args.charset is not None),
                             ("--mask", args.mask is not None), ("--wordlist", args.wordlist is not None),
+                            ("--wordlist2", args.wordlist2 is not None),
                             ("--rules", args.rules is not None), ("--stdout", args.stdout), ("--owner", args.owner),
                             ("--key", args.key is not None), ("-1 .. -4", any(c is not None for c in customs))):
             if given:
@@ -865,6 +1007,21 @@ def main(argv=None):
             known = key40.known_key(args.key)
         except ValueError as ex:
             parser.error("--key: %s" % ex)
+    if args.wordlist2 is not None:
+        if args.wordlist is None:
+            parser.error("--wordlist2 is the right side of a combinator search: it needs a --wordlist, the left side")
+        for flag, given in (("--mask", args.mask is not None), ("--rules", args.rules is not None),
+                            ("-pr/--passwordrange", args.passwordrange is not None),
+                            ("--charset", args.charset is not None)):
+            if given:
+                parser.error("--wordlist2 multiplies two wordlists: it cannot be combined with %s" % flag)
+        for flag, rule in (("--rule-left", args.rule_left), ("--rule-right", args.rule_right)):
+            try:
+                _side_rule(rule)
+            except rulemod.RuleError as ex:
+                parser.error("%s: %s" % (flag, ex))
+    elif args.rule_left is not None or args.rule_right is not None:
+        parser.error("--rule-left and --rule-right belong to a combinator search: give --wordlist2")
     if args.rules is not None:
         if args.wordlist is None:
             parser.error("--rules needs a --wordlist: rules are applied to its words")
@@ -907,6 +1064,17 @@ def main(argv=None):
         if not found:
             print("No key of the searched window verifies.")
         return found, key
+    if args.wordlist2 is not None and args.stdout:
+        n = print_combine_candidates(parse_verification_data(stream), args.wordlist, args.wordlist2, args.rule_left,
+                                     args.rule_right, devices=devices)
+        return 0, n
+    if args.wordlist2 is not None:
+        found, password = init(stream, None, None, devices=devices, checkpoint=args.checkpoint, owner=args.owner,
+                               wordlist=args.wordlist, key=known, wordlist2=args.wordlist2, rule_left=args.rule_left,
+                               rule_right=args.rule_right)
+        if not found:
+            print("Password is not in brute-forced space.")
+        return found, password
     if args.rules is not None and args.stdout:
         n = print_rule_candidates(parse_verification_data(stream), args.wordlist, args.rules, devices=devices)
         return 0, n

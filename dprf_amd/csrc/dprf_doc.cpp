@@ -1003,6 +1003,31 @@ uint32_t rules_longest(const dprf_doc *c, const uint32_t *fns, const uint32_t *r
     return std::min<uint32_t>(best * unit, fam(c->kind).trunc);
 }
 
+/* ------------------------------------------------------------------ combinator windows */
+int check_combine(const dprf_doc *c, const char *who, uint64_t start, uint64_t count) {
+    if (c->nwords == 0) return fail(DPRF_E_INVALID, "%s: the context has no left word table (dprf_ctx_set_words)", who);
+    if (c->nright == 0)
+        return fail(DPRF_E_INVALID, "%s: the context has no right word table (dprf_ctx_set_right_words)", who);
+    if ((unsigned __int128)start + count > (unsigned __int128)c->nwords * c->nright)
+        return fail(DPRF_E_INVALID, "window [%llu, +%llu) exceeds the combinator keyspace of %llu left times %llu right words",
+                    (unsigned long long)start, (unsigned long long)count, (unsigned long long)c->nwords,
+                    (unsigned long long)c->nright);
+    /* the sum cannot wrap: a table's converted bytes stay below 2^32 in all */
+    const uint64_t longest = std::min<uint64_t>(c->w_longest + c->r_longest, fam(c->kind).trunc);
+    if (longest > SLOT_BYTES) {
+        char detail[160];
+        snprintf(detail, sizeof detail, ": left word %llu takes %llu bytes, right word %llu takes %llu",
+                 (unsigned long long)c->w_longest_idx, (unsigned long long)c->w_longest,
+                 (unsigned long long)c->r_longest_idx, (unsigned long long)c->r_longest);
+        return check_slot("combinator", longest, detail);
+    }
+    return DPRF_OK;
+}
+
+uint32_t combine_longest(const dprf_doc *c) {
+    return (uint32_t)std::min<uint64_t>(std::min<uint64_t>(c->w_longest + c->r_longest, fam(c->kind).trunc), SLOT_BYTES);
+}
+
 }   // namespace dprf_internal
 
 /* ------------------------------------------------------------------ ABI: chunk planning by family name */

@@ -115,6 +115,10 @@ struct dprf_doc {
      * word before the clip to a slot, which decides whether a mask fits */
     uint64_t nwords = 0;
     uint64_t w_longest = 0, w_longest_idx = 0;
+    /* the right table of combinator searches (dprf_ctx_set_right_words), kept as the table above is: that one is the
+     * left table there */
+    uint64_t nright = 0;
+    uint64_t r_longest = 0, r_longest_idx = 0;
 };
 
 /* What policy() and plan_chunk() take as `iterations` for this document */
@@ -171,6 +175,13 @@ uint64_t start_digits(uint64_t v, const uint32_t *radix, int npos, uint32_t *sdi
 int check_rules(const dprf_doc *c, const char *who, const uint32_t *fns, const uint32_t *rule_off, int64_t nrules,
                 uint64_t start, uint64_t count);
 uint32_t rules_longest(const dprf_doc *c, const uint32_t *fns, const uint32_t *rule_off, int64_t nrules);
+
+/* What dprf_search_combine and dprf_spell_combine refuse alike (include/dprf.h "combinator mode"); `who` names the
+ * export: a missing table, a window above nwords * nright (in 128 bits: DPRF_E_INVALID), and two longest words that do
+ * not share a slot after the format's cut (DPRF_E_PWLEN). */
+int check_combine(const dprf_doc *c, const char *who, uint64_t start, uint64_t count);
+/* The longest candidate of a combinator window, after the cut (check_combine has bounded it by a slot) */
+uint32_t combine_longest(const dprf_doc *c);
 
 }   // namespace dprf_internal
 #endif

@@ -1,9 +1,10 @@
 /* dprf_kernels_spell.hip -- the device spellers: index g of a chunk -> the candidate's bytes in a list slot, for the
- * list-mode kernels of every family to verify.  Four candidate sources, one block of 256 lanes per 256 candidates:
+ * list-mode kernels of every family to verify.  Five candidate sources, one block of 256 lanes per 256 candidates:
  *   k_spell_symbols  symbol windows (dprf_search_symbols)                   uniform radix over one symbol table
  *   k_spell_mask     mask windows (dprf_search_mask)                        a radix and a symbol list per position
  *   k_spell_hybrid   hybrid windows (dprf_search_hybrid)                    a word of the context's table in a mask
  *   k_spell_rules    rule windows (dprf_search_rules, dprf_spell_rules)     a rule of the call applied to a word
+ *   k_spell_combine  combinator windows (dprf_search_combine, dprf_spell_combine)  a left word, then a right word
  * What they share is written once, here and in the helpers below.
  *
  * The slot tile.  A block's 256 slots sit in LDS as [word][slot] with a row stride of ST = 258 words; lane t owns
@@ -41,7 +42,9 @@
  *   k_spell_mask     records 512 + pool 8,192 + 2,048 + tile 16,512                 = 27,264 B   6 blocks (24 waves)
  *   k_spell_hybrid   the mask kernel's + offsets 1,028 + run 16,388 + ends 8        = 44,704 B   3 blocks (12 waves)
  *   k_spell_rules    two tiles 33,024 + offsets 1,028 + run 16,388 + ends 8         = 50,452 B   3 blocks (12 waves)
- * No kernel uses scratch (resource_gate.py).
+ *   k_spell_combine  tile 16,512 + left offsets 1,028 + run 16,388 + ends 8
+ *                    + right entries 1,024 + run 16,388 (+ 28 alignment)              = 51,376 B   3 blocks (12 waves)
+ * No kernel uses scratch (resource_gate.py).  k_spell_combine: 37 VGPRs.
  */
 #include "dev_crypto.h"
 #include "dprf_params.h"
@@ -486,6 +489,106 @@ k_spell_rules(dprf_rules_args a, const uint32_t *fns, const uint32_t *roff, cons
     read_out(tile, tid, base, a.count, slots);
 }
 
+/* ================================================================== combinator windows */
+/* Candidate g of the chunk is left word a.l0 + (a.r0 + g) / N2 followed by right word (a.r0 + g) % N2 (N2 = a.nright):
+ * the chunk start's two indices travel in the arguments and the division is the rules kernel's multiply-high
+ * (a.r0 + g < 2^32: N2 < 2^31, a chunk holds at most 2^26 candidates).
+ *
+ * The left words of a block do not decrease with g: one contiguous run of at most 256 words, staged by stage_run as
+ * the hybrid and rules kernels stage theirs.  The right words of a block are R0, R0 + 1, ... modulo N2, R0 being lane
+ * 0's.  For N2 <= 256 the block may cycle through the table several times, so the whole table is staged and a lane's
+ * entry is its right index; for N2 > 256 the block wraps at most once, so the words from R0 to the table's end and
+ * then those from word 0 are staged, two byte ranges back to back in rrun[], and a lane's entry is (R - R0) mod N2.
+ * Either way at most 256 words and 16 KB, copied with consecutive loads; no lane gathers word bytes from global memory.
+ * An entry of rent[] is the word's first byte in rrun[] (bits 0-15) and its length (bits 16-23), written by the lane of
+ * the same number and clamped where it is read: the length to a slot, the first byte to a slot or more before the end
+ * of rrun[] -- whatever the offsets say, as in find_word.  R0 is recomputed by every lane from the block's base (a
+ * block-uniform value), so the right run needs no published ends. */
+__global__ void __launch_bounds__(256)
+k_spell_combine(dprf_combine_args a, const uint32_t *lblob, const uint32_t *loff, const uint32_t *rblob,
+                const uint32_t *roff, uint32_t *slots, uint8_t *lens) {
+    __shared__ uint32_t tile[TW];
+    __shared__ uint32_t soff[DPRF_HYB_RUN + 1];
+    __shared__ uint32_t run[DPRF_HYB_RUN_WORDS];
+    __shared__ uint32_t ends[2];
+    __shared__ uint32_t rent[DPRF_HYB_RUN];
+    __shared__ uint32_t rrun[DPRF_HYB_RUN_WORDS];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t base = blockIdx.x * 256u;
+    const uint32_t g = base + tid;
+    const bool live = g < a.count;
+    const uint32_t lim = a.trunc < 4u * DPRF_SLOT_WORDS ? a.trunc : 4u * DPRF_SLOT_WORDS;
+    const uint32_t N2 = a.nright ? a.nright : 1u;
+    tile_clear(tile, tid);
+    /* lane 0's right word: the same value in every lane */
+    const uint32_t idx0 = a.r0 + base;
+    const uint32_t q0 = N2 == 1u ? idx0 : fastdiv(idx0, a.div_m, a.div_s);
+    uint32_t R0 = idx0 - q0 * N2;
+    R0 = R0 < N2 ? R0 : N2 - 1u;
+    uint32_t L = 0, R = 0;
+    if (live) {
+        const uint32_t idx = a.r0 + g;
+        const uint32_t q = N2 == 1u ? idx : fastdiv(idx, a.div_m, a.div_s);
+        R = idx - q * N2;
+        R = R < N2 ? R : N2 - 1u;
+        L = a.l0 + q;
+        L = L < a.nleft ? L : a.nleft - 1u;
+    }
+    {
+        /* the right run: words [first, first + n1) and then [0, n2) of the table.  The roff[] reads below stay at or
+         * under index N2: that roff[] holds a.nright + 1 offsets is the host's word (dprf_ctx_set_right_words uploads
+         * both together), the one thing here no clamp guarantees -- as a.nwords and woff[] in stage_run */
+        const uint32_t left = a.count > base ? a.count - base : 1u;
+        const uint32_t nlive = left < 256u ? left : 256u;
+        const bool whole = N2 <= DPRF_HYB_RUN;
+        const uint32_t first = whole ? 0u : R0;
+        const uint32_t n1 = whole ? N2 : (nlive < N2 - R0 ? nlive : N2 - R0);
+        const uint32_t n2 = whole ? 0u : nlive - n1;
+        const uint32_t b0 = roff[first], b1 = roff[first + n1];
+        const uint32_t a0 = b0 >> 2;
+        uint32_t nu1 = b1 > 4u * a0 ? (b1 - 4u * a0 + 3u) >> 2 : 0u;
+        nu1 = nu1 < DPRF_HYB_RUN_WORDS ? nu1 : DPRF_HYB_RUN_WORDS;
+        nu1 = a0 < a.rbwords ? (nu1 < a.rbwords - a0 ? nu1 : a.rbwords - a0) : 0u;
+        const uint32_t c0 = roff[0], c1 = roff[n2];
+        const uint32_t e0 = c0 >> 2;
+        uint32_t nu2 = n2 && c1 > 4u * e0 ? (c1 - 4u * e0 + 3u) >> 2 : 0u;
+        nu2 = nu2 < DPRF_HYB_RUN_WORDS - nu1 ? nu2 : DPRF_HYB_RUN_WORDS - nu1;
+        nu2 = e0 < a.rbwords ? (nu2 < a.rbwords - e0 ? nu2 : a.rbwords - e0) : 0u;
+        for (uint32_t k = tid; k < nu1; k += 256u) rrun[k] = rblob[a0 + k];
+        for (uint32_t k = tid; k < nu2; k += 256u) rrun[nu1 + k] = rblob[e0 + k];
+        uint32_t ent = 0u;
+        if (tid < n1 + n2) {
+            const bool one = tid < n1;
+            const uint32_t wk = one ? first + tid : tid - n1;
+            const uint32_t o0 = roff[wk], o1 = roff[wk + 1u];
+            const uint32_t wl = o1 > o0 ? o1 - o0 : 0u;
+            const uint32_t at = one ? o0 - 4u * a0 : 4u * nu1 + (o0 - 4u * e0);
+            ent = (at & 0xffffu) | ((wl < 4u * DPRF_SLOT_WORDS ? wl : 4u * DPRF_SLOT_WORDS) << 16);
+            ent = at < 0x10000u ? ent : 0u;
+        }
+        rent[tid] = ent;
+    }
+    /* the left run; its last barrier also covers the right run's stores and the cleared tile */
+    const word_run r = stage_run(live, L, tid, base, a.count, a.lbwords, lblob, loff, ends, soff, run);
+    if (live) {
+        uint32_t wl;
+        const uint32_t lsrc = find_word(r, L, soff, wl);
+        const uint32_t d = N2 <= DPRF_HYB_RUN ? R : (R >= R0 ? R - R0 : R + (N2 - R0));
+        const uint32_t ent = rent[d < DPRF_HYB_RUN ? d : DPRF_HYB_RUN - 1u];
+        uint32_t rl = (ent >> 16) & 0xffu;
+        rl = rl < 4u * DPRF_SLOT_WORDS ? rl : 4u * DPRF_SLOT_WORDS;
+        uint32_t rsrc = ent & 0xffffu;
+        rsrc = rsrc <= 4u * DPRF_HYB_RUN_WORDS - 4u * DPRF_SLOT_WORDS ? rsrc : 0u;
+        const uint8_t *lb = (const uint8_t *)run, *rb = (const uint8_t *)rrun;
+        for (uint32_t j = 0; j < wl; j++) put_byte(tile, tid, j, lim, lb[lsrc + j]);
+        for (uint32_t j = 0; j < rl; j++) put_byte(tile, tid, wl + j, lim, rb[rsrc + j]);
+        const uint32_t total = wl + rl;
+        lens[g] = (uint8_t)(total < lim ? total : lim);
+    }
+    __syncthreads();
+    read_out(tile, tid, base, a.count, slots);
+}
+
 /* ------------------------------------------------------------------ launchers (dprf_launch.h) */
 static dim3 blocks_of(uint32_t count) { return dim3((count + 255u) / 256u); }
 
@@ -513,5 +616,11 @@ hipError_t launch_spell_rules(const dprf_rules_args &a, const uint32_t *fns, con
     else
         hipLaunchKernelGGL(k_spell_rules<1>, blocks_of(a.count), dim3(256), 0, s, a, fns, roff, wblob, woff, slots,
                            lens);
+    return hipGetLastError();
+}
+hipError_t launch_spell_combine(const dprf_combine_args &a, const uint32_t *lblob, const uint32_t *loff,
+                                const uint32_t *rblob, const uint32_t *roff, uint32_t *slots, uint8_t *lens,
+                                hipStream_t s) {
+    hipLaunchKernelGGL(k_spell_combine, blocks_of(a.count), dim3(256), 0, s, a, lblob, loff, rblob, roff, slots, lens);
     return hipGetLastError();
 }

@@ -49,7 +49,7 @@ hipError_t launch_collide_oldoffice(const dprf_enum &e, const dprf_oldoffice_par
 /* long list (e.mode 2): the records' first-message hash into e.keys, or (DPRF_LONG_R5) the whole R5 check */
 hipError_t launch_long_prehash(const dprf_enum &e, const dprf_long_params &lp, dprf_results *R, uint32_t cap,
                                uint32_t stop, hipStream_t s);
-/* The four device spellers (dprf_kernels_spell.hip), each into slots[n][DPRF_SLOT_WORDS] / lens[n]; bytes at or past
+/* The device spellers (dprf_kernels_spell.hip), each into slots[n][DPRF_SLOT_WORDS] / lens[n]; bytes at or past
  * the trunc of the arguments stay zero. */
 /* symbol windows (dprf_search_symbols): e.count candidates from the digits in e.sdig (base e.cslen), symbol table
  * symtab = [256] LE-packed bytes + [256] byte counts */
@@ -69,6 +69,12 @@ hipError_t launch_spell_hybrid(const dprf_hybrid_args &a, const uint32_t *tab, c
 hipError_t launch_spell_rules(const dprf_rules_args &a, const uint32_t *fns, const uint32_t *roff,
                               const uint32_t *wblob, const uint32_t *woff, uint32_t *slots, uint8_t *lens,
                               hipStream_t s);
+/* combinator windows (dprf_search_combine / dprf_spell_combine): a.count candidates, left word a.l0 + (a.r0 + g) /
+ * a.nright of (lblob, loff: a.nleft + 1 byte offsets) followed by right word (a.r0 + g) % a.nright of (rblob, roff:
+ * a.nright + 1 byte offsets) */
+hipError_t launch_spell_combine(const dprf_combine_args &a, const uint32_t *lblob, const uint32_t *loff,
+                                const uint32_t *rblob, const uint32_t *roff, uint32_t *slots, uint8_t *lens,
+                                hipStream_t s);
 hipError_t launch_pdf_r6(const dprf_enum &e, const dprf_pdf_params &p, const dprf_aes_tables *T,
                          dprf_results *R, uint32_t cap, uint32_t stop, hipStream_t s);
 #endif

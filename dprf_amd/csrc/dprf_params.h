@@ -105,6 +105,21 @@ struct dprf_rules_args {
     uint32_t bwords;                /* u32 words the device blob holds (the staging loads stay below it) */
 };
 
+/* Combinator windows (dprf_search_combine / dprf_spell_combine, k_spell_combine): a word of the context's left table
+ * (dprf_ctx_set_words) followed by a word of its right table (dprf_ctx_set_right_words), both stored on the device as the
+ * hybrid table is.  Candidate g of a launch is left word l0 + (r0 + g) / nright followed by right word (r0 + g) %
+ * nright; r0 + g stays below 2^32 (nright < 2^31, a launch holds at most 2^26 candidates). */
+struct dprf_combine_args {
+    uint32_t count;                 /* candidates of the launch */
+    uint32_t trunc;                 /* bytes at or past it are never written (PDF R2-R4 32, R5 127, else ~0) */
+    uint32_t l0;                    /* the chunk start's left word index */
+    uint32_t r0;                    /* the chunk start's right word index, < nright */
+    uint32_t nleft;                 /* words in the left table (>= 1) */
+    uint32_t nright;                /* words in the right table (>= 1, < 2^31) */
+    uint32_t div_m, div_s;          /* u32 division by nright (fastdiv_magic; unused for nright = 1) */
+    uint32_t lbwords, rbwords;      /* u32 words the left / right device blob holds (the staging loads stay below) */
+};
+
 /* Device results of one API call (accumulated over its launches). */
 struct dprf_results {
     uint32_t nhits;                 /* total hits (may exceed cap) */

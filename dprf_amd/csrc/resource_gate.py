@@ -38,6 +38,7 @@ SCRATCH_LIMIT = {
     "k_agile_check": 0,
     "k_spell_hybrid": 0,      # ... hybrid windows (dprf_search_hybrid)
     "k_spell_rules": 0,       # ... rule windows (dprf_search_rules / dprf_spell_rules)
+    "k_spell_combine": 0,     # ... combinator windows (dprf_search_combine / dprf_spell_combine)
     "k_oldoffice": 0,         # Office 97-2003 RC4 / RC4 CryptoAPI (dprf_kernels_oldoffice.hip)
     "k_odf_bf_kdf": 0,        # ODF 1.0 / 1.1 Blowfish-CFB (dprf_kernels_odf.hip)
     "k_odf_bf_check": 0,

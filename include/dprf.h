@@ -495,6 +495,44 @@ int dprf_search_rules(dprf_ctx *ctx, const uint32_t *fns, const uint32_t *rule_o
 int dprf_spell_rules(dprf_ctx *ctx, const uint32_t *fns, const uint32_t *rule_off, int64_t nrules, uint64_t start,
                      uint64_t count, uint8_t *slots, uint8_t *lens);
 
+/* ---- combinator mode: a word table times a second word table ("summer" + "2024", "Anna" + "Maria") ----
+ * Additive to ABI 9 (DPRF_ABI_VERSION stays 9): a caller detects it by looking the symbol dprf_search_combine up.
+ * This is hashcat's -a 1.
+ *
+ * The tables.  The left table is the context's word table (dprf_ctx_set_words, unchanged).  The right table is a second
+ * one with the same validation, conversion, storage and life cycle: Office words go from UTF-8 to UTF-16LE, the other
+ * formats keep their bytes, a word is stored clipped to a 64-byte slot, and the table goes to every device of the
+ * context, where it stays until it is replaced, cleared (n = 0) or the context is destroyed.  dprf_ctx_set_right_words
+ * refuses what dprf_ctx_set_words refuses, and n >= 2^31 as DPRF_E_INVALID (the device divides a right index plus a
+ * chunk's candidate index as 32 bits); a refused table leaves the previous one in place.  It takes the context's call
+ * mutex.  Neither setter touches the other table.  dprf_ctx_right_words returns the number of right words held (0: no
+ * table); dprf_words_status serves both tables.
+ *
+ * The keyspace.  With N1 left and N2 right words, candidate i of the keyspace N1 * N2 is left word i / N2 followed by
+ * right word i % N2: the left word is the slowest digit, as the word is in hybrid and rule mode.  The bytes are the
+ * concatenation, and the format's truncation applies to the whole candidate (PDF R2-R4 32 bytes, R5 127).
+ *
+ * dprf_search_combine verifies indices [start, start + count).  Nothing but the chunk start's two word indices goes up
+ * per launch; the device spells every candidate into a list slot from the two tables it holds (k_spell_combine) and
+ * the list-mode kernels verify the slots.  hits[] relative to `start`, stop_on_first (the lowest verifying index),
+ * multi-device chunks, the cross-device stop, stats, the per-device records, owner mode, a set key40 and
+ * DPRF_FLAG_NEVER_MATCHES contexts are as dprf_search_hybrid's.
+ * dprf_spell_combine is the counterpart of dprf_spell_rules: slot k of slots[count * 64] holds the bytes of candidate
+ * start + k after the format's cut (Office: UTF-16LE), zero-padded, and lens[k] their number, spelled by the same
+ * kernel on the context's first device; no verification kernel runs.  count <= 2^20.
+ * Errors (a refused call leaves no per-device record, and the context still serves):
+ * DPRF_E_INVALID -- a null argument, either table missing (the message says which), start + count above N1 * N2
+ * (computed in 128 bits); for dprf_spell_combine also count above 2^20 or a never-matching context.
+ * DPRF_E_PWLEN -- min(the longest converted left word + the longest converted right word, the truncation) exceeds a
+ * 64-byte slot; the message names both words by index and gives their converted lengths.  Where the truncation is at
+ * most 64 bytes (R2-R4) tables of any word lengths are accepted.
+ * Not done: a mask around the pair, more than two tables, candidates over 64 bytes. */
+int dprf_ctx_set_right_words(dprf_ctx *ctx, const uint8_t *blob, const uint64_t *offsets, int64_t n);
+int64_t dprf_ctx_right_words(const dprf_ctx *ctx);
+int dprf_search_combine(dprf_ctx *ctx, uint64_t start, uint64_t count, int stop_on_first, uint64_t *hits, int64_t cap,
+                        int64_t *nhits, dprf_stats *stats);
+int dprf_spell_combine(dprf_ctx *ctx, uint64_t start, uint64_t count, uint8_t *slots, uint8_t *lens);
+
 /* ---- 40-bit key search: the candidate is the RC4 key itself ----
  * Additive to ABI 9 (DPRF_ABI_VERSION stays 9): a caller detects it by looking the symbol dprf_search_key40 up.
  * Four of the families protect the document with only 40 bits of RC4 key, however long the password is, so the keys
@@ -552,13 +590,13 @@ int dprf_search_key40(dprf_ctx *ctx, uint64_t start, uint64_t count, int stop_on
  *   Office 97-2003 type 3             h = SHA1(salt || pw16); k = SHA1(h || 00 00 00 00);  k[0:5] == K
  * Truncation and candidate lengths are those of the family's password search: PDF cuts at 32 bytes, Office takes at
  * most 32 UTF-16 units in a slot and more is DPRF_E_PWLEN.
- * While a key is set dprf_search_range, dprf_search_symbols, dprf_search_mask, dprf_verify_list, dprf_search_hybrid and
- * dprf_search_rules verify against K, with hit indices, stop_on_first, multi-device chunks, the cross-device stop, stats,
- * the per-device records and dprf_list_status as before.  Several candidates of one window may verify -- that is the
- * purpose -- and all are reported, ascending.  key == NULL clears the key and restores the document check exactly.
- * dprf_search_key40 and dprf_spell_rules are unaffected by the selection.  The setter takes the context's call mutex (it
- * waits for a running call).  dprf_ctx_key40 returns 1 and writes the five bytes (key may be NULL) when a key is set,
- * else 0.
+ * While a key is set dprf_search_range, dprf_search_symbols, dprf_search_mask, dprf_verify_list, dprf_search_hybrid,
+ * dprf_search_rules and dprf_search_combine verify against K, with hit indices, stop_on_first, multi-device chunks,
+ * the cross-device stop, stats, the per-device records and dprf_list_status as before.  Several candidates of one
+ * window may verify -- that is the purpose -- and all are reported, ascending.  key == NULL clears the key and
+ * restores the document check exactly.  dprf_search_key40, dprf_spell_rules and dprf_spell_combine are unaffected by
+ * the selection.  The setter takes the context's call mutex (it waits for a running call).  dprf_ctx_key40 returns 1
+ * and writes the five bytes (key may be NULL) when a key is set, else 0.
  * Errors (neither changes the selection, and the context still serves): DPRF_E_DOMAIN -- the document is not a 40-bit
  * one, with dprf_search_key40's sentence; DPRF_E_INVALID -- a PDF context in owner mode: a key collider finds the user
  * password.  dprf_ctx_set_pdf_password(ctx, DPRF_PDF_OWNER) while a key is set is DPRF_E_INVALID likewise.  A
